@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark of the per-pixel hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps once (`ms_per_step` = that time / K), writes the outputs of the last
+timed step if --dump-outputs is given, and prints the line.  --full adds, at N = 1, what the line carried before it was
+made lean: the median of --trials (default 10) repetitions of the K steps, the frames verified against one-frame renders,
+the work counters and the roofline object (with live `rocprofv3 --pmc` passes and the vector-memory probes), the latency
+form, the host-readback forms and the CPU baseline.  An N > 1 line always carries its verification, stages and both root
+modes.
+
+--dump-outputs DIR writes the last timed frame (the frame a caller of the timed path receives last) as DIR/frame.npy,
+float32 [height, width, 4]; a frame larger than 64 MB is written as a fixed, seeded sample of its pixels instead
+(DIR/frame_sample.npy, float32 [n, 4], and DIR/frame_sample_pixels.npy, float64 flat pixel indices).  The inputs are
+seeded: the same arguments give the same inputs in every run.
 
 Workload (BASELINE.json configs[1]): bunny-class mesh (69,168 triangles, written as trisrc text and loaded
 through the real parser + BVH builder), seeded HDR sky environment, 1920x1080, 1 spp, default gold material,
@@ -53,6 +65,8 @@ PMC_FILE = os.path.join("profiles", "r06", "pmc_headline.json")   # written by p
 ISA_COSTS = os.path.join("profiles", "r06", "isa_costs.json")     # written by profiles/isa_costs.py from the kernels' ISA
 VMEM_MIX = os.path.join("profiles", "r06", "vmem_class_mix.json")  # distinct records per vector-memory instruction, measured (histogram builds)
 WARM_SECONDS = 0.15        # back-to-back frames before the first trial, beyond the W warm-up steps: the GPU's clock ramps
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 20251015  # --dump-outputs: the pixel sample of a frame above the limit
 
 
 def log(*a):
@@ -335,8 +349,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--trials", type=int, default=10,
-                    help="the timed K-step loop is repeated this many times (each bracketed by barrier + synchronize); the median trial is reported")
+    ap.add_argument("--trials", type=int, default=None,
+                    help="the timed K-step loop is repeated this many times (each bracketed by barrier + synchronize); the median trial is "
+                         "reported (default: 1, with --full 10)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also the verified frames, work counters, roofline (live counter passes, probes), latency and host-readback "
+                         "forms and the CPU baseline, and 10 trials by default (a plain run times the K steps once and reports that)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed frame to DIR/frame.npy (float32; a seeded pixel sample above 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel", type=int, default=0)
     ap.add_argument("--width", type=int, default=WIDTH, help="frame width (default: the headline configuration)")
@@ -349,12 +369,12 @@ def main():
                     help="consecutive frames per launch (shray_render_batch_device / shray_dist_step).  Default: 4 for "
                          "N = 1, 4 N for N > 1 (a step then carries four frames' worth of pixels per GPU; 2 N when --steps < 16 N)")
     ap.add_argument("--root-mode", choices=["rotate", "root0"], default="rotate",
-                    help="N > 1: rotate = frame f of a step is assembled on rank f % N (all-to-all over every xGMI link); "
+                    help="N > 1: rotate = frame f of a step is assembled on rank f %% N (all-to-all over every xGMI link); "
                          "root0 = every frame on rank 0 (gather)")
     ap.add_argument("--rgba-wire", action="store_true", help="N > 1 only: exchange RGBA instead of RGB (alpha is the constant 1)")
     ap.add_argument("--same-view", action="store_true", help="every frame renders the first view of the orbit (round 2's loop)")
     ap.add_argument("--no-live-counters", action="store_true",
-                    help="N = 1: take the roofline's instruction and byte counts from the committed counter file only (default: "
+                    help="N = 1 with --full: take the roofline's instruction and byte counts from the committed counter file only (default: "
                          "measure them in this invocation with short `rocprofv3 --pmc` child runs after the timed region, ~30 s)")
     ap.add_argument("--counter-child", action="store_true", help=argparse.SUPPRESS)   # the child run live_counters() profiles
     ap.add_argument("--rank-timeout", type=float, default=300.0,
@@ -362,6 +382,10 @@ def main():
                          '{"error": "rank timeout", ...} is printed and the exit code is 124 (0 = no budget)')
     args = ap.parse_args()
     WIDTH, HEIGHT, SPP = args.width, args.height, args.spp
+    if args.trials is None:
+        args.trials = 10 if args.full else 1
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, args.rank_timeout))
@@ -592,7 +616,7 @@ def main():
         for trial in range(trials):
             fence()
             t0 = time.perf_counter()
-            run(args.steps, timed=trial)
+            run(args.steps, timed=trial if args.full else None)    # (the launch events feed the --full roofline only)
             fence()
             dt = time.perf_counter() - t0
             if distributed:
@@ -655,6 +679,32 @@ def main():
                 differing += 0 if torch.equal(frame_outs[0][k * HEIGHT * WIDTH * 4:(k + 1) * HEIGHT * WIDTH * 4], whole) else 1
         return compared, differing
 
+    def dump_last_frame(directory):
+        """The last frame of the last timed trial, as its launch left it (no render of its own), written as float32 by the
+        rank that holds it; a frame above DUMP_LIMIT_BYTES goes out as a fixed, seeded sample of its pixels."""
+        import numpy as np
+        launches = -(-args.steps // batch)
+        lane = (launches - 1) % lanes
+        count = args.steps - (launches - 1) * batch       # frames of the last launch; the last step is its frame count - 1
+        torch.cuda.synchronize()
+        if distributed:
+            frame = active["rank"].frames(lane, count, streams[lane].cuda_stream).get(count - 1)
+            torch.cuda.synchronize()
+        else:
+            pixels = HEIGHT * WIDTH * 4
+            frame = frame_outs[lane][(count - 1) * pixels:count * pixels]
+        if frame is None:          # N > 1: another rank assembled it
+            return
+        frame = frame.reshape(HEIGHT, WIDTH, 4).cpu().numpy().astype(np.float32, copy=False)
+        os.makedirs(directory, exist_ok=True)
+        if frame.nbytes <= DUMP_LIMIT_BYTES - 4096:         # (4 KB for the .npy headers)
+            np.save(os.path.join(directory, "frame.npy"), frame)
+            return
+        n = (DUMP_LIMIT_BYTES - 4096) // (4 * 4 + 8)      # an RGBA float32 pixel and its float64 index
+        picked = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(HEIGHT * WIDTH, size=n, replace=False))
+        np.save(os.path.join(directory, "frame_sample.npy"), frame.reshape(-1, 4)[picked])
+        np.save(os.path.join(directory, "frame_sample_pixels.npy"), picked.astype(np.float64))
+
     if args.counter_child:
         # what live_counters() profiles: exactly `steps` frames of the timed loop's launches (whole periods of the orbit), nothing else
         run(args.steps)
@@ -662,6 +712,9 @@ def main():
         return
     stage("warm-up and timed trials (shray_dist_step: render, pack, grouped exchange, de-interleave)" if distributed else "timed trials")
     trial_s, warm_ms, warm_frames = timed_trials()
+    if args.dump_outputs:
+        stage("writing the outputs of the last timed step")
+        dump_last_frame(args.dump_outputs)
     elapsed = sorted(trial_s)[len(trial_s) // 2]
     alt = None
     stages = stages_report(trial_s, me) if distributed else None
@@ -680,9 +733,13 @@ def main():
                    "what": ("every frame gathered on rank 0 (north_star's gather; link-bound at 1 spp: DESIGN.md section 6)"
                             if name == "root0" else "frame f of a step assembled on rank f % N (all-to-all over every xGMI link)")}
         active["rank"] = me
-    stage("frame verification")
-    frames_compared, frames_differing = verify_frames()
-    stage("counters, roofline and the report")
+    # what the headline figure does not need: at N = 1 only with --full (an N > 1 line always carries its verification)
+    extras = args.full or distributed
+    frames_compared = frames_differing = None
+    if extras:
+        stage("frame verification")
+        frames_compared, frames_differing = verify_frames()
+    stage("counters, roofline and the report" if extras else "the report")
 
     result = None
     frames_per_s = args.steps / elapsed
@@ -695,11 +752,10 @@ def main():
             "value": round(rays / elapsed / 1e6, 3), "unit": "Mrays/s", "n_gpus": world_size, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 5), "higher_is_better": True,
             "trials": trials, "trial_ms": [round(t * 1e3, 4) for t in trial_s],
-            "timing": f"median of {trials} trials of exactly {args.steps} steps, each between barrier + synchronize fences; "
+            "timing": (f"median of {trials} trials" if trials > 1 else "one trial") + f" of exactly {args.steps} steps, each between barrier + synchronize fences; "
                       f"after the {args.warmup} warm-up steps the loop ran untimed for {warm_ms:.0f} ms ({warm_frames} frames) so that the "
                       "clock has ramped before the first trial",
             "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "frames_verified": frames_compared - frames_differing, "frames_mismatched": frames_differing,
             "rccl_ranks": rccl_ranks, "transport_fallback": transport_fallback, "scene_turnaround": turnaround,
             "config": {"workload": "bunny-class trisrc (69,168 triangles, synthetic stand-in for bunny.trisrc) + seeded "
                                    f"2048x1024 HDR sky, {WIDTH}x{HEIGHT}, {SPP} spp, "
@@ -714,9 +770,12 @@ def main():
                        "wire": ("rgb32f" if not args.rgba_wire else "rgba32f") if distributed else None},
         }
 
+    if rank == 0 and frames_compared is not None:
+        result.update({"frames_verified": frames_compared - frames_differing, "frames_mismatched": frames_differing})
+
     # work counters of the orbit: the counting kernels' (the reference's traversals, equal to the CPU oracle's) and
     # the timed instances' own (shadow rays stop at their first hit; equal for the gold headline)
-    if rank == 0:
+    if rank == 0 and extras:
         sums, timed_sums = {}, {}
         for view in (orbit[:1] if args.same_view else orbit):
             _, c = scene.render_counters(view, WIDTH, HEIGHT, SPP, want_image=False)
@@ -924,7 +983,7 @@ def main():
             roof["counter_source"] = "not collected for N > 1 (see the N = 1 line)"
         result["roofline"] = roof
 
-    if not distributed:
+    if not distributed and extras:
         # one frame at a time, in the same run: the latency form of the loop (one frame per launch, no second stream).
         # `ms`: 2 x ORBIT launches back to back on one stream (each starts when the one before it has drained);
         # `ms_host_synchronised`: the host waits for every frame before it submits the next

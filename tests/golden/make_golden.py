@@ -8,6 +8,10 @@ Writes, next to this script:
   <scene>.ref.npz     the REFERENCE's flattened arrays + frame parameters for each, dumped
                       by oracle/_ref/ref_host (the reference's own loader / BVH / flattener /
                       view-parameter code compiled where it lies)
+  bunny_class_132x264.ref.npz, small_sphere_40x64.ref.npz   the same dumps for the benchmark-sized scenes the
+                      package generates (scenes.bunny_trisrc, scenes.small_obj_no_normals), with the SHA-256 of
+                      the generated file under `input_sha256`; the bunny-class scene's arrays of more than 64
+                      floats are stored as SHA-256 digests of their bits (`<name>.sha256`, `<name>.size`)
   lobed_528.oracle.npz  64x64 frames of the small trisrc scene rendered by the CPU oracle
                       (gold and glazed plaster) -- regression vectors for the GPU path;
                       they pin the oracle's output at the time of commit, not the reference
@@ -71,6 +75,19 @@ def dump_reference(scene_path, out_npz):
     np.savez_compressed(out_npz, **d)
 
 
+def dump_generated_reference(scene_path, out_npz, digest_above=None):
+    """dump_reference for a scene file the package generates (not committed): the file's hash goes with the dump, and
+    with `digest_above` every array of more floats is stored as its bit digest (refdump.digest_large)."""
+    import hashlib
+    from refdump import digest_large
+    dump_reference(scene_path, out_npz)
+    d = dict(np.load(out_npz))
+    if digest_above is not None:
+        d = digest_large(d, digest_above)
+    d["input_sha256"] = np.array(hashlib.sha256(open(scene_path, "rb").read()).hexdigest())
+    np.savez_compressed(out_npz, **d)
+
+
 def main():
     pkg = load_package()
     subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "all"], check=True, stdout=subprocess.DEVNULL)
@@ -85,6 +102,9 @@ def main():
 
     for path in (tri_path, mixed, nonorm):
         dump_reference(path, os.path.splitext(path)[0] + ".ref.npz")
+    # (the bunny-class scene's arrays, 9.8 MB, go in as digests; the small sphere's whole)
+    for path, digest_above in ((pkg.scenes.bunny_trisrc(), 64), (pkg.scenes.small_obj_no_normals(), None)):
+        dump_generated_reference(path, os.path.join(HERE, os.path.splitext(os.path.basename(path))[0] + ".ref.npz"), digest_above)
 
     world = pkg.World(tri_path)
     desc = world.flatten()

@@ -218,14 +218,14 @@ def test_shader_constants_as_parameters(pkg, gpu, oracle_mod, material):
 
 
 def test_bench_line_carries_the_frozen_roofline_object(gpu):
-    """`python bench.py` (N = 1) prints ONE line whose `roofline` has the round-5 definition: hbm / vmem / valu, each
+    """`python bench.py --full` (N = 1) prints ONE line whose `roofline` has the round-5 definition: hbm / vmem / valu, each
     achieved over peak, the top-level pair = the largest of the three; its instruction and byte counts come from `rocprofv3 --pmc`
     passes the command runs on its own child processes in the same invocation, and agree with the committed counter file of the same
     device code to a fraction of a per cent (the counts of a deterministic kernel)."""
     import json
     bench = os.path.join(ROOT, "bench.py")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    run = subprocess.run([sys.executable, bench, "--steps", "20", "--warmup", "4", "--trials", "3", "--no-cpu-baseline"], env=env,
+    run = subprocess.run([sys.executable, bench, "--full", "--steps", "20", "--warmup", "4", "--trials", "3", "--no-cpu-baseline"], env=env,
                          capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stderr[-3000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.strip()]
@@ -243,3 +243,34 @@ def test_bench_line_carries_the_frozen_roofline_object(gpu):
     if agree:       # the committed counter file is of this build: the same counts
         assert all(abs(v - 1.0) < 0.01 for v in agree.values()), agree
     assert not any(key.endswith("_busy") for key in roof if key != "busy_profiled")
+
+
+def test_plain_bench_line_and_its_dumped_outputs(pkg, gpu, tmp_path):
+    """A plain `python bench.py` times exactly --steps steps once and carries only the headline fields; --dump-outputs writes
+    the last timed frame, which is the one-frame render of that step's view of the orbit, bit for bit."""
+    import json
+    W, H, steps = 320, 180, 7
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = tmp_path / "dump"
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2",
+                          "--width", str(W), "--height", str(H), "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0, run.stderr[-3000:]
+    lines = [ln for ln in run.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f32" and line["value"] > 0
+    assert line["steps"] == steps and line["trials"] == 1 and len(line["trial_ms"]) == 1
+    assert abs(line["ms_per_step"] - line["trial_ms"][0] / steps) < 1e-3
+    assert "roofline" not in line and "cpu_baseline" not in line and "latency" not in line
+    assert sorted(os.listdir(out)) == ["frame.npy"]
+    frame = np.load(out / "frame.npy")
+    assert frame.dtype == np.float32 and frame.shape == (H, W, 4)
+    # bench.py's orbit: the start-up view dragged (0.025, 0.010) further every frame; step k renders view k % 20
+    world = pkg.World(pkg.scenes.bunny_trisrc())
+    view = world.default_view()
+    view.which_material = 0
+    for _ in range(steps):
+        pkg.host.trackball_motion(view.object_rotation, 0.025, 0.010)
+    scene = pkg.Scene(world.flatten(), pkg.scenes.environment_hdr_sky(2048), device=0)
+    assert np.array_equal(frame, scene.render(world.frame_params(W, H, view), W, H, 1))
+    scene.close()

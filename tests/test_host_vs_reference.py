@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import helpers
-from refdump import read_dump
+from refdump import bits_sha256, read_dump
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,6 +32,10 @@ def check_world_against(pkg, scene_path, ref):
     for k in SCALARS:
         assert int(ref[k][0]) == int(mine[k]), k
     for k in ARRAYS:
+        if k + ".sha256" in ref:      # a large scene's fixture holds the digest of the array's bits (refdump.digest_large)
+            assert mine[k].ndim == 1 and mine[k].size == int(ref[k + ".size"]), k
+            assert bits_sha256(mine[k]) == str(ref[k + ".sha256"]), f"{k}: the bits differ from the reference's"
+            continue
         assert mine[k].shape == ref[k].shape, k
         diff = int((bits(mine[k]) != bits(ref[k])).sum())
         assert diff == 0, f"{k}: {diff} of {mine[k].size} floats differ from the reference"
@@ -66,13 +70,28 @@ def test_against_committed_reference_dumps(pkg, name):
     check_world_against(pkg, path, ref)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_HOST), reason="oracle/_ref/ref_host not built (needs /root/reference)")
 @pytest.mark.parametrize("which", ["bunny", "obj_small"])
 def test_against_live_reference(pkg, tmp_path, which):
+    """The benchmark-sized scenes the package generates, against the reference's dump of the same files: committed
+    (tests/golden/<scene>.ref.npz, keyed by the generated file's SHA-256; the bunny-class scene's large arrays as digests
+    of their bits) and, where oracle/_ref/ref_host is built, live as well -- the live dump must then equal the committed
+    one bit for bit."""
+    import hashlib
     path = helpers.bunny_trisrc() if which == "bunny" else helpers.small_obj_no_normals()
-    dump = str(tmp_path / "ref.bin")
-    subprocess.run([REF_HOST, path, dump, "1920", "1080"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    check_world_against(pkg, path, read_dump(dump))
+    ref = dict(np.load(os.path.join(GOLDEN, os.path.splitext(os.path.basename(path))[0] + ".ref.npz")))
+    assert hashlib.sha256(open(path, "rb").read()).hexdigest() == str(ref.pop("input_sha256")), \
+        f"{path} is not the file the committed dump was made from: run tests/golden/make_golden.py"
+    check_world_against(pkg, path, ref)
+    if os.path.exists(REF_HOST):
+        dump = str(tmp_path / "ref.bin")
+        subprocess.run([REF_HOST, path, dump, "1920", "1080"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        live = read_dump(dump)
+        assert sorted(live) == sorted(k[:-len(".sha256")] if k.endswith(".sha256") else k for k in ref if not k.endswith(".size"))
+        for k in live:
+            if k + ".sha256" in ref:
+                assert live[k].size == int(ref[k + ".size"]) and bits_sha256(live[k]) == str(ref[k + ".sha256"]), k
+            else:
+                assert np.array_equal(bits(live[k]), bits(ref[k])), k
 
 
 def test_survey_probe_values_unit_sphere(pkg, tmp_path):
