@@ -12,6 +12,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # SHRAY_HOST_LIB selects another build of the host layer (the sanitizer build, `make -C shader-ray_amd sanitize`: tests/test_sanitizers.py)
 HOST_LIB = os.environ.get("SHRAY_HOST_LIB") or os.path.join(PKG_DIR, "libshray_host.so")
 DIST_LIB = os.path.join(PKG_DIR, "libshray_dist.so")
+QUERY_LIB = os.path.join(PKG_DIR, "libshray_query.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
 HIP_LIB = os.environ.get("SHRAY_HIP_LIB") or os.path.join(PKG_DIR, "libshray_hip.so")
 
@@ -232,9 +233,36 @@ DIST_SYMBOLS = [
     ("shray_dist_copy_to_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 ]
 
+# include/shader_ray_query.h ------------------------------------------------------------------------------
+HIT_MISS, HIT_CAP = -1, -2
+
+
+class Ray(C.Structure):
+    """shray_ray: object-space origin, tmax, direction, one reserved float (32 bytes)."""
+    _fields_ = [("origin", C.c_float * 3), ("tmax", C.c_float), ("direction", C.c_float * 3), ("reserved", C.c_float)]
+
+
+class Hit(C.Structure):
+    """shray_hit: t, u, v, triangle (HIT_MISS, HIT_CAP or the scene's triangle index)."""
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("triangle", C.c_int32)]
+
+
+class QueryParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_bvh_iterations", C.c_int32), ("max_leaf_tests", C.c_int32), ("any_hit", C.c_int32)]
+
+
+QUERY_SYMBOLS = [
+    ("shray_query_params_init", None, [C.POINTER(QueryParams)]),
+    ("shray_trace_rays_device", C.c_int, [C.c_void_p, C.POINTER(QueryParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("shray_trace_rays", C.c_int, [C.c_void_p, C.POINTER(QueryParams), C.c_void_p, C.c_int64, C.c_void_p]),
+    ("shray_trace_rays_counters", C.c_int, [C.c_void_p, C.POINTER(QueryParams), C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(Counters)]),
+    ("shray_primary_hits_device", C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+]
+
 _host = None
 _hip = None
 _dist = None
+_query = None
 
 
 def _bind(lib, table):
@@ -282,6 +310,17 @@ def load_dist():
             raise RuntimeError(f"{DIST_LIB} is not built; run `python __graft_entry__.py build` (or `make -C shader-ray_amd`)")
         _dist = _bind(C.CDLL(DIST_LIB), DIST_SYMBOLS)
     return _dist
+
+
+def load_query():
+    """Loads the ray-query library (libshray_query.so: a client of libshray_hip.so; its errors are read with shray_last_error)."""
+    global _query
+    if _query is None:
+        load_hip()
+        if not os.path.exists(QUERY_LIB):
+            raise RuntimeError(f"{QUERY_LIB} is not built; run `python __graft_entry__.py build` (or `make -C shader-ray_amd`)")
+        _query = _bind(C.CDLL(QUERY_LIB), QUERY_SYMBOLS)
+    return _query
 
 
 def check_dist(code: int):

@@ -17,6 +17,7 @@
 #include "launch.h"
 #include "packed_layout.h"
 #include "device_tree_internal.h"
+#include "scene_access_internal.h"
 #include "shader_ray_hip.h"
 
 using namespace shray;
@@ -1450,6 +1451,24 @@ int shray_scene_device(const shray_scene *scene, int *device_index)
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene or device_index is NULL");
     *device_index = scene->device;
     return SHRAY_OK;
+}
+
+int shrayi_scene_query_view(const shray_scene *scene, ShrayQueryScene *out)
+{
+    if (!scene || !out)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene is NULL");
+    out->view = scene->view;
+    out->stack_levels = scene->stack_levels;
+    out->packed_ok = scene->packed_ok;
+    out->kernel_id = scene->kernel_id;
+    out->device = scene->device;
+    return SHRAY_OK;
+}
+
+int shrayi_frame_view(const shray_frame_params *params, int width, int height, FrameView *out)
+{
+    const int rc = validate_params(params, width, height, 1);
+    return rc ? rc : make_frame_view(params, width, height, 1, nullptr, out);
 }
 
 int shray_scene_set_kernel(shray_scene *scene, int kernel_id)

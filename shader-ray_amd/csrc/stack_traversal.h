@@ -60,15 +60,17 @@ struct StackTraversal {
     // the rest of the walk finds -- a closer hit, or the iteration cap's bad hit (t = -1) -- so the ray stops there.
     // The counting twins walk on: their tallies are compared with the reference's full traversal -- unless they are
     // asked for the tallies of the timed form itself (TIMED_FORM).
+    // bound: the running closest hit's starting value (lane_begin): kFar for the shader's rays, a ray query's tmax; the
+    // any-hit exit tests against it
     template <bool COUNT, bool ANY_HIT = false, bool TIMED_FORM = false>
     __device__ __forceinline__ int closest(const SceneView &sc, const FrameView &fr, bool has_ray, V3 P, V3 D, Hit &hit,
-                                           RayCounters &rc)
+                                           RayCounters &rc, float bound = kFar)
     {
         const int traced = __popcll(wave_ballot(has_ray));
         if (!traced)
             return 0;
         LaneTraversal t;
-        lane_begin<COUNT>(sc, fr, t, stack, P, D, rc, has_ray);
+        lane_begin<COUNT>(sc, fr, t, stack, P, D, rc, has_ray, bound);
         int state = has_ray ? LT_WALK : LT_ENDED;
         if (PAIR) {
             // the root's visit (its own box, fs:395's first iteration) is made by the first retest stage
@@ -80,7 +82,7 @@ struct StackTraversal {
                     rc.leaf_visits++;
             }
         }
-        run<COUNT, true, ANY_HIT && (!COUNT || TIMED_FORM)>(sc, fr, t, state, rc);
+        run<COUNT, true, ANY_HIT && (!COUNT || TIMED_FORM)>(sc, fr, t, state, rc, bound);
         hit = t.hit;
         return traced;
     }
@@ -98,7 +100,8 @@ struct StackTraversal {
 
     // CONVERGED: every lane of the wave is executing (the dealt leaf stage may use them all)
     template <bool COUNT, bool CONVERGED, bool ANY_HIT = false>
-    __device__ __forceinline__ void run(const SceneView &sc, const FrameView &fr, LaneTraversal &t, int &state, RayCounters &rc)
+    __device__ __forceinline__ void run(const SceneView &sc, const FrameView &fr, LaneTraversal &t, int &state, RayCounters &rc,
+                                        float bound = kFar)
     {
         do {
 #if defined(SHRAY_DIAGNOSTICS) && !defined(SHRAY_DIAG_KHIST) && !defined(SHRAY_DIAG_UNIFORM)
@@ -127,7 +130,7 @@ struct StackTraversal {
                 leaf_stage_dealt<COUNT, BLOCK, PAIR, CACHE, ROOMY>(sc, fr, t, state, stack, rc, ids SHRAY_DIAG_ARG);
             else
                 leaf_stage<COUNT, BLOCK, PAIR, CACHE>(sc, fr, t, state, stack, rc, ids SHRAY_DIAG_ARG);
-            if (ANY_HIT && state != LT_ENDED && t.hit.t < kFar)
+            if (ANY_HIT && state != LT_ENDED && t.hit.t < bound)
                 state = LT_ENDED;   // a hit: the shadow query is answered (a capped ray, t = -1, has ended already)
 #if defined(SHRAY_DIAGNOSTICS) && !defined(SHRAY_DIAG_KHIST) && !defined(SHRAY_DIAG_UNIFORM)
             const unsigned long long c2 = __builtin_amdgcn_s_memtime();

@@ -111,9 +111,11 @@ __device__ __forceinline__ uint32_t octant_offset(const SceneView &sc, bool fx, 
 __device__ __forceinline__ uint32_t node_address(const LaneTraversal &t, uint32_t node) { return (node << kNodeNameShift) + t.octant; }
 
 // group_intersect set-up for the object-space ray (P, D)                      (fs:388-392, :486)
+// bound: where the running closest hit starts -- the shader's infinitely_far, or a ray query's own tmax (query/ray_query.hip;
+// at most kRangeMax there: the scheduled node stage's integer compare takes hit.t in place of the range's end, visit_asm.h)
 template <bool COUNT>
 __device__ __forceinline__ void lane_begin(const SceneView &sc, const FrameView &fr, LaneTraversal &t, uint32_t *stack, V3 P, V3 D,
-                                           RayCounters &rc, bool counted = true)
+                                           RayCounters &rc, bool counted = true, float bound = kFar)
 {
     t.P = P;
     t.D = D;
@@ -135,7 +137,7 @@ __device__ __forceinline__ void lane_begin(const SceneView &sc, const FrameView 
     t.fz = D.z >= 0.0f;
     t.positive_dir = (D.x > 0.0f ? 1u : 0u) | (D.y > 0.0f ? 2u : 0u) | (D.z > 0.0f ? 4u : 0u);
     t.octant = octant_offset(sc, t.fx, t.fy, t.fz);
-    t.hit = Hit{kFar, -1.0f, 0.0f, 0.0f};
+    t.hit = Hit{bound, -1.0f, 0.0f, 0.0f};
     t.node = sc.packed_root;
     t.top = stack;
     t.left = fr.max_bvh_iterations > 0 ? fr.max_bvh_iterations : 0x7fffffff;   // counted down to the cap; never zero without one

@@ -1,0 +1,367 @@
+// ray_query.hip -- include/shader_ray_query.h: caller-supplied object-space rays through the scene's BVH, one hit record each.
+//
+// The walk is the renderer's own, from the product's headers (csrc/): the packed stack traversal in its convergent form
+// (StackTraversal::closest: the dealt leaf stage and the hand-scheduled node and leaf stages of the timed instances), or the
+// literal threaded traversal (kernel id 1, or a scene without a packed tree).  The one difference from the shader's traversal
+// is where the running closest hit starts: at the ray's tmax (clamped to the range's end, 1e8 -- see the header) instead of
+// infinitely_far.  This library is built apart from libshray_hip.so, so the renderer's code objects do not change.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+
+#include "kernel_stack_common.h"
+#include "scene_access_internal.h"
+#include "shader_ray_query.h"
+#include "threaded_traversal.h"
+
+extern "C" int shrayi_fail(int code, const char *message);   // capi.hip: sets shray_last_error()
+
+using namespace shray;
+
+namespace {
+
+int fail(int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return shrayi_fail(code, buf);
+}
+
+#define HIP_TRY(expr)                                                                                                  \
+    do {                                                                                                               \
+        const hipError_t e_ = (expr);                                                                                  \
+        if (e_ != hipSuccess)                                                                                          \
+            return fail(e_ == hipErrorOutOfMemory ? SHRAY_ERR_OUT_OF_MEMORY : SHRAY_ERR_DEVICE, "%s failed: %s", #expr, \
+                        hipGetErrorString(e_));                                                                        \
+    } while (0)
+
+constexpr int kThreadedBlock = 256;
+// rays per launch: a larger count is split (the grid's threads must stay below 2^32; and a launch of this size fills the
+// machine many times over, so the split costs nothing measurable)
+constexpr uint64_t kRaysPerLaunch = 1ull << 24;
+
+// What a kernel works on: rays from memory, or the primary rays of a frame in 8 x 8 (stack) / 16 x 16 (threaded) pixel tiles.
+struct QueryWork {
+    const float4 *rays;   // 2 float4 per ray; nullptr: primary rays of `fr`
+    float4 *hits;         // (t, u, v, triangle bits)
+    uint64_t count;       // rays, or pixels
+    uint64_t first_block; // of this launch
+    DeviceCounters *counters;
+};
+
+// The ray of work item i, or the pixel ray of the lane in tile `tile`.  Returns false for a lane without a work item.
+template <int TILE>
+__device__ __forceinline__ bool query_ray(const FrameView &fr, const QueryWork &w, uint64_t block, V3 &P, V3 &D, float &tmax,
+                                          uint64_t &index)
+{
+    if (w.rays) {
+        index = block * (uint64_t)(TILE * TILE) + threadIdx.x;
+        if (index >= w.count)
+            return false;
+        const float4 a = w.rays[2 * index], b = w.rays[2 * index + 1];
+        P = mk(a.x, a.y, a.z);
+        tmax = a.w;
+        D = mk(b.x, b.y, b.z);
+        return true;
+    }
+    // trace_pixels (trace_common.h) at one sample: the pixel-centre ray, then the object transform of trace_ray
+    const unsigned int tiles_x = ((unsigned int)fr.width + TILE - 1u) / TILE;
+    const int px = (int)((block % tiles_x) * TILE + threadIdx.x % TILE);
+    const int py = (int)((block / tiles_x) * TILE + threadIdx.x / TILE);
+    if (px >= fr.width || py >= fr.height)
+        return false;
+    index = (uint64_t)py * (uint64_t)fr.width + (uint64_t)px;
+    const float u = ((float)px + 0.5f) / (float)fr.width;
+    const float v = ((float)py + 0.5f) / (float)fr.height;
+    const V3 eye = unit(mk(fr.image_plane_width * (u - 0.5f), fr.image_plane_width * (v - 0.5f) * fr.aspect, -1.0f));
+    const V3 Pw = xform(fr.camera_matrix, mk(0, 0, 0), 1.0f);
+    const V3 Dw = unit(xform(fr.camera_normal_matrix, eye, 0.0f));
+    P = xform(fr.object_matrix, Pw, 1.0f);
+    D = xform(fr.object_normal_matrix, Dw, 0.0f);
+    tmax = kFar;
+    return true;
+}
+
+// The walk's result as a hit record (header: semantics).  traced = the ray was walked (tmax > 0).
+__device__ __forceinline__ float4 hit_record(const Hit &hit, bool traced, float tmax)
+{
+    int triangle;
+    float t = hit.t;
+    if (traced && hit.t == -1.0f) {
+        triangle = SHRAY_HIT_CAP;
+    } else if (traced && hit.which >= 0.0f && hit.t < tmax) {
+        triangle = (int)hit.which;
+    } else {
+        triangle = SHRAY_HIT_MISS;
+        if (!(hit.which >= 0.0f))
+            t = tmax;   // nothing accepted: the bound the walk started from (before its clamp to the range's end)
+    }
+    return make_float4(t, hit.bu, hit.bv, __int_as_float(triangle));
+}
+
+// the walk starts from min(tmax, 1e8) (the header explains why that is the same walk)
+__device__ __forceinline__ float start_bound(float tmax) { return tmax < kRangeMax ? tmax : kRangeMax; }
+
+// kernel id 0: one-wave workgroups, the convergent packed stack traversal (every lane of the wave enters closest() together).
+// COUNT: the counting instance (the compiler's node stage, the cap in front of every visit, every ray walked to its end).
+template <bool COUNT, bool ANY_HIT>
+__global__ void __launch_bounds__(kBatchBlock, COUNT ? SHRAY_MIN_WAVES_VIEW : SHRAY_MIN_WAVES_DEALT)
+    query_stack_kernel(SceneView sc, FrameView fr, QueryWork w, int stack_levels)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+    using Traversal = StackTraversal<kBatchBlock, true, false, false, false>;
+    Traversal trav = make_traversal<true, kBatchBlock, false, false, false>(lds_stack, stack_levels);
+    V3 P = mk(0, 0, 0), D = mk(0, 0, 1);
+    float tmax = 0.0f;
+    uint64_t index = 0;
+    const bool live = query_ray<8>(fr, w, w.first_block + blockIdx.x, P, D, tmax, index);
+    const bool traced = live && tmax > 0.0f;   // (false for NaN)
+    const float bound = traced ? start_bound(tmax) : kFar;
+    Hit hit{bound, -1.0f, 0.0f, 0.0f};
+    RayCounters rc = {0, 0, 0, 0, 0, 0, 0};
+    trav.template closest<COUNT, ANY_HIT && !COUNT>(sc, fr, traced, P, D, hit, rc, bound);
+    if (live)
+        w.hits[index] = hit_record(hit, traced, tmax);
+    if (COUNT) {
+        if (traced && hit.t == -1.0f)
+            rc.bad_hits++;
+        add_counters(rc, w.counters);
+    }
+}
+
+// kernel id 1: the literal threaded traversal, one ray per thread (any-hit rays are walked to their end: the closest hit is
+// an any-hit answer)
+template <bool COUNT>
+__global__ void __launch_bounds__(kThreadedBlock) query_threaded_kernel(SceneView sc, FrameView fr, QueryWork w)
+{
+    V3 P = mk(0, 0, 0), D = mk(0, 0, 1);
+    float tmax = 0.0f;
+    uint64_t index = 0;
+    const bool live = query_ray<16>(fr, w, w.first_block + blockIdx.x, P, D, tmax, index);
+    const bool traced = live && tmax > 0.0f;
+    Hit hit{traced ? start_bound(tmax) : kFar, -1.0f, 0.0f, 0.0f};
+    RayCounters rc = {0, 0, 0, 0, 0, 0, 0};
+    ThreadedTraversal trav;
+    if (traced)
+        trav.closest<COUNT>(sc, fr, P, D, hit, rc);
+    if (live)
+        w.hits[index] = hit_record(hit, traced, tmax);
+    if (COUNT) {
+        if (traced && hit.t == -1.0f)
+            rc.bad_hits++;
+        add_counters(rc, w.counters);   // (every lane of the wave is here)
+    }
+}
+
+int check_params(const shray_query_params *qp)
+{
+    if (!qp)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "query params are NULL");
+    if (qp->struct_size != sizeof(shray_query_params))
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "shray_query_params.struct_size is %u, this library expects %zu", qp->struct_size,
+                    sizeof(shray_query_params));
+    if (qp->max_bvh_iterations < 0 || qp->max_bvh_iterations > (1 << 24) || qp->max_leaf_tests < 0 || qp->max_leaf_tests > (1 << 24) ||
+        (qp->any_hit != 0 && qp->any_hit != 1))
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "query params out of range (max_bvh_iterations %d, max_leaf_tests %d, any_hit %d)",
+                    qp->max_bvh_iterations, qp->max_leaf_tests, qp->any_hit);
+    return SHRAY_OK;
+}
+
+int scene_of(shray_scene *scene, ShrayQueryScene *q)
+{
+    if (!scene)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene is NULL");
+    const int rc = shrayi_scene_query_view(scene, q);
+    if (rc)
+        return rc;
+    int current = -1;
+    if (hipGetDevice(&current) != hipSuccess || current != q->device)
+        HIP_TRY(hipSetDevice(q->device));   // the scene's buffers live on its device
+    return SHRAY_OK;
+}
+
+bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+
+// `blocks` workgroups of work `w` (first_block = 0), in launches of at most kRaysPerLaunch threads
+int launch_query(const ShrayQueryScene &q, const FrameView &fr, QueryWork w, uint64_t blocks, bool any_hit, hipStream_t stream)
+{
+    const bool stack = q.packed_ok && q.kernel_id != 1;
+    const int block = stack ? kBatchBlock : kThreadedBlock;
+    const uint64_t per_launch = kRaysPerLaunch / (uint64_t)block;
+    const size_t lds = stack ? stack_lds_bytes(q.stack_levels, kBatchBlock) : 0;
+    const bool count = w.counters != nullptr;
+    for (uint64_t first = 0; first < blocks; first += per_launch) {
+        w.first_block = first;
+        const dim3 grid((unsigned int)(blocks - first < per_launch ? blocks - first : per_launch));
+        if (stack && count)
+            hipLaunchKernelGGL((query_stack_kernel<true, false>), grid, dim3(block), lds, stream, q.view, fr, w, q.stack_levels);
+        else if (stack && any_hit)
+            hipLaunchKernelGGL((query_stack_kernel<false, true>), grid, dim3(block), lds, stream, q.view, fr, w, q.stack_levels);
+        else if (stack)
+            hipLaunchKernelGGL((query_stack_kernel<false, false>), grid, dim3(block), lds, stream, q.view, fr, w, q.stack_levels);
+        else if (count)
+            hipLaunchKernelGGL((query_threaded_kernel<true>), grid, dim3(block), 0, stream, q.view, fr, w);
+        else
+            hipLaunchKernelGGL((query_threaded_kernel<false>), grid, dim3(block), 0, stream, q.view, fr, w);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return fail(SHRAY_ERR_DEVICE, "ray query launch failed: %s", hipGetErrorString(e));
+    }
+    return SHRAY_OK;
+}
+
+// the query's FrameView: only the traversal's two constants are read (0 = no cap: a cap nothing reaches)
+FrameView query_frame(const shray_query_params *qp)
+{
+    FrameView fr;
+    memset(&fr, 0, sizeof(fr));
+    fr.max_bvh_iterations = qp->max_bvh_iterations > 0 ? qp->max_bvh_iterations : INT_MAX;
+    fr.max_leaf_tests = qp->max_leaf_tests;
+    return fr;
+}
+
+int trace_device(shray_scene *scene, const shray_query_params *qp, const shray_ray *d_rays, int64_t count, shray_hit *d_hits,
+                 hipStream_t stream, DeviceCounters *d_counters)
+{
+    int rc = check_params(qp);
+    if (rc)
+        return rc;
+    if (count < 0)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "negative ray count %lld", (long long)count);
+    if (!scene || !d_rays || !d_hits)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene, rays or hits is NULL");
+    if (!aligned16(d_rays) || !aligned16(d_hits))
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "ray and hit buffers must be 16-byte aligned");
+    if (count == 0)
+        return SHRAY_OK;
+    ShrayQueryScene q;
+    rc = scene_of(scene, &q);
+    if (rc)
+        return rc;
+    const bool stack = q.packed_ok && q.kernel_id != 1;
+    const uint64_t block = stack ? kBatchBlock : kThreadedBlock;
+    QueryWork w{(const float4 *)d_rays, (float4 *)d_hits, (uint64_t)count, 0, d_counters};
+    return launch_query(q, query_frame(qp), w, ((uint64_t)count + block - 1) / block, qp->any_hit != 0, stream);
+}
+
+// the blocking forms: the rays to the device, the query on the null stream, the hits (and tallies) back
+int trace_host(shray_scene *scene, const shray_query_params *qp, const shray_ray *rays, int64_t count, shray_hit *hits,
+               shray_counters *out)
+{
+    int rc = check_params(qp);
+    if (rc)
+        return rc;
+    if (count < 0)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "negative ray count %lld", (long long)count);
+    if (!scene || !rays || (!hits && !out))
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene, rays or hits is NULL");
+    if (out) {
+        memset(out, 0, sizeof(*out));
+        out->samples = (uint64_t)count;
+    }
+    if (count == 0)
+        return SHRAY_OK;
+    ShrayQueryScene q;
+    rc = scene_of(scene, &q);
+    if (rc)
+        return rc;
+    struct Buffers {
+        void *rays = nullptr, *hits = nullptr, *counters = nullptr;
+        ~Buffers()
+        {
+            for (void *p : {rays, hits, counters})
+                if (p)
+                    (void)hipFree(p);
+        }
+    } b;
+    const size_t ray_bytes = (size_t)count * sizeof(shray_ray), hit_bytes = (size_t)count * sizeof(shray_hit);
+    HIP_TRY(hipMalloc(&b.rays, ray_bytes));
+    HIP_TRY(hipMalloc(&b.hits, hit_bytes));
+    if (out) {
+        HIP_TRY(hipMalloc(&b.counters, sizeof(DeviceCounters) * kCounterShards));
+        HIP_TRY(hipMemset(b.counters, 0, sizeof(DeviceCounters) * kCounterShards));
+    }
+    HIP_TRY(hipMemcpy(b.rays, rays, ray_bytes, hipMemcpyHostToDevice));
+    rc = trace_device(scene, qp, (const shray_ray *)b.rays, count, (shray_hit *)b.hits, nullptr, (DeviceCounters *)b.counters);
+    if (rc)
+        return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (hits)
+        HIP_TRY(hipMemcpy(hits, b.hits, hit_bytes, hipMemcpyDeviceToHost));
+    if (out) {
+        DeviceCounters shards[kCounterShards];
+        HIP_TRY(hipMemcpy(shards, b.counters, sizeof(shards), hipMemcpyDeviceToHost));
+        for (const DeviceCounters &s : shards) {
+            out->node_visits += s.node_visits;
+            out->leaf_visits += s.leaf_visits;
+            out->triangle_tests += s.triangle_tests;
+            out->traversals += s.traversals;
+            out->bad_hits += s.bad_hits;
+        }
+    }
+    return SHRAY_OK;
+}
+
+}   // namespace
+
+extern "C" {
+
+void shray_query_params_init(shray_query_params *qp)
+{
+    if (!qp)
+        return;
+    qp->struct_size = sizeof(shray_query_params);
+    qp->max_bvh_iterations = 400;   // fs:426
+    qp->max_leaf_tests = 10;        // fs:405
+    qp->any_hit = 0;
+}
+
+int shray_trace_rays_device(shray_scene *scene, const shray_query_params *qp, const shray_ray *d_rays, int64_t count,
+                            shray_hit *d_hits, void *hip_stream)
+{
+    return trace_device(scene, qp, d_rays, count, d_hits, (hipStream_t)hip_stream, nullptr);
+}
+
+int shray_trace_rays(shray_scene *scene, const shray_query_params *qp, const shray_ray *rays, int64_t count, shray_hit *hits)
+{
+    if (!hits && count > 0)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "hits is NULL");
+    return trace_host(scene, qp, rays, count, hits, nullptr);
+}
+
+int shray_trace_rays_counters(shray_scene *scene, const shray_query_params *qp, const shray_ray *rays, int64_t count,
+                              shray_hit *hits, shray_counters *out)
+{
+    if (!out)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "counters is NULL");
+    return trace_host(scene, qp, rays, count, hits, out);
+}
+
+int shray_primary_hits_device(shray_scene *scene, const shray_frame_params *params, int width, int height, shray_hit *d_hits,
+                              void *hip_stream)
+{
+    if (!scene || !params || !d_hits)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene, params or hits is NULL");
+    if (!aligned16(d_hits))
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "the hit buffer must be 16-byte aligned");
+    FrameView fr;
+    int rc = shrayi_frame_view(params, width, height, &fr);
+    if (rc)
+        return rc;
+    ShrayQueryScene q;
+    rc = scene_of(scene, &q);
+    if (rc)
+        return rc;
+    const uint64_t tile = (q.packed_ok && q.kernel_id != 1) ? 8u : 16u;
+    const uint64_t blocks = (((uint64_t)width + tile - 1) / tile) * (((uint64_t)height + tile - 1) / tile);
+    QueryWork w{nullptr, (float4 *)d_hits, (uint64_t)width * (uint64_t)height, 0, nullptr};
+    return launch_query(q, fr, w, blocks, false, (hipStream_t)hip_stream);
+}
+
+}   // extern "C"

@@ -134,6 +134,48 @@ class Scene:
             self._handle, C.byref(params), width, height, spp,
             C.byref(tiles) if tiles is not None else None, C.c_void_p(out_ptr), C.c_void_p(stream_ptr)))
 
+    def trace_rays(self, rays, tmax=None, any_hit: bool = False, max_bvh_iterations: int = 400, max_leaf_tests: int = 10,
+                   counters: bool = False):
+        """Ray queries from host memory (shray_trace_rays, blocking).  `rays`: a RAY_DTYPE array, or [n, 6] / [n, 8] float32
+        (origin, direction / the shray_ray layout); `tmax` (scalar or [n]) replaces the rays' own.  Returns a HIT_DTYPE array,
+        and with counters=True also the walk's counters (shray_trace_rays_counters)."""
+        rays = np.asarray(rays)
+        if rays.dtype != RAY_DTYPE:
+            a = np.asarray(rays, np.float32)
+            if a.ndim != 2 or a.shape[1] not in (6, 8):
+                raise ValueError("rays must be a RAY_DTYPE array or [n, 6] (origin, direction) / [n, 8] (shray_ray) float32")
+            rays = make_rays(a[:, 0:3], a[:, 3:6]) if a.shape[1] == 6 else np.ascontiguousarray(a).view(RAY_DTYPE).reshape(-1)
+        rays = np.ascontiguousarray(rays).copy() if tmax is not None else np.ascontiguousarray(rays)
+        if tmax is not None:
+            rays["tmax"] = np.asarray(tmax, np.float32)
+        hits = np.empty(len(rays), HIT_DTYPE)
+        qp = query_params(any_hit, max_bvh_iterations, max_leaf_tests)
+        lib = N.load_query()
+        if counters:
+            c = N.Counters()
+            N.check(lib.shray_trace_rays_counters(self._handle, C.byref(qp), rays.ctypes.data_as(C.c_void_p), len(rays),
+                                                  hits.ctypes.data_as(C.c_void_p), C.byref(c)))
+            return hits, c.as_dict()
+        N.check(lib.shray_trace_rays(self._handle, C.byref(qp), rays.ctypes.data_as(C.c_void_p), len(rays), hits.ctypes.data_as(C.c_void_p)))
+        return hits
+
+    def trace_rays_into(self, rays_ptr: int, count: int, hits_ptr: int, stream_ptr: int = 0, any_hit: bool = False,
+                        max_bvh_iterations: int = 400, max_leaf_tests: int = 10):
+        """Asynchronous ray queries on device memory (shray_trace_rays_device): `count` shray_ray records at `rays_ptr`
+        (e.g. a float32 [n, 8] tensor's data_ptr()) -> `count` shray_hit records at `hits_ptr` (e.g. [n, 4] float32 / int32),
+        on a HIP stream (`stream_ptr`, e.g. torch.cuda.current_stream().cuda_stream)."""
+        qp = query_params(any_hit, max_bvh_iterations, max_leaf_tests)
+        N.check(N.load_query().shray_trace_rays_device(self._handle, C.byref(qp), C.c_void_p(rays_ptr), count, C.c_void_p(hits_ptr),
+                                                       C.c_void_p(stream_ptr)))
+
+    def primary_hits(self, params: N.FrameParams, width: int, height: int) -> np.ndarray:
+        """The hit of every pixel's 1-spp primary ray (shray_primary_hits_device): HIT_DTYPE [height, width], row 0 = bottom."""
+        import torch
+        out = torch.empty((height * width, 4), dtype=torch.int32, device="cuda")
+        N.check(N.load_query().shray_primary_hits_device(self._handle, C.byref(params), width, height, C.c_void_p(out.data_ptr()),
+                                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return np.ascontiguousarray(out.cpu().numpy()).view(HIT_DTYPE).reshape(height, width)
+
     def render_batch_into(self, params_list, width: int, height: int, spp: int, out_ptr: int, frame_stride_bytes: int,
                           stream_ptr: int = 0, tiles: N.TileSet | None = None):
         """`len(params_list)` frames in one launch; frame k goes to out_ptr + k * frame_stride_bytes
@@ -144,6 +186,28 @@ class Scene:
             self._handle, array, count, width, height, spp,
             C.byref(tiles) if tiles is not None else None, C.c_void_p(out_ptr), frame_stride_bytes,
             C.c_void_p(stream_ptr)))
+
+
+# a ray buffer / hit array of the query (include/shader_ray_query.h): 32 and 16 bytes per element
+RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("tmax", np.float32), ("direction", np.float32, 3), ("reserved", np.float32)])
+HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), ("triangle", np.int32)])
+
+
+def make_rays(origins, directions, tmax=None) -> np.ndarray:
+    """A RAY_DTYPE array from [n, 3] origins and directions; tmax: a scalar or [n] (default 1e7, the shader's infinitely_far)."""
+    origins = np.asarray(origins, np.float32).reshape(-1, 3)
+    rays = np.zeros(len(origins), RAY_DTYPE)
+    rays["origin"] = origins
+    rays["direction"] = np.asarray(directions, np.float32).reshape(-1, 3)
+    rays["tmax"] = np.float32(1e7) if tmax is None else np.asarray(tmax, np.float32)
+    return rays
+
+
+def query_params(any_hit: bool = False, max_bvh_iterations: int = 400, max_leaf_tests: int = 10) -> N.QueryParams:
+    qp = N.QueryParams()
+    N.load_query().shray_query_params_init(C.byref(qp))
+    qp.max_bvh_iterations, qp.max_leaf_tests, qp.any_hit = max_bvh_iterations, max_leaf_tests, 1 if any_hit else 0
+    return qp
 
 
 class DeviceFlat:
@@ -247,6 +311,18 @@ class DeviceWorld:
         desc = N.SceneDesc()
         N.check(self._hip.shray_device_flat_download(self._flat, C.byref(desc)))
         return desc_arrays(desc)
+
+    def trace_rays(self, rays, **kwargs):
+        """Scene.trace_rays on this scene."""
+        return self.scene.trace_rays(rays, **kwargs)
+
+    def trace_rays_into(self, rays_ptr: int, count: int, hits_ptr: int, stream_ptr: int = 0, **kwargs):
+        """Scene.trace_rays_into on this scene."""
+        return self.scene.trace_rays_into(rays_ptr, count, hits_ptr, stream_ptr, **kwargs)
+
+    def primary_hits(self, params: N.FrameParams, width: int, height: int) -> np.ndarray:
+        """Scene.primary_hits on this scene."""
+        return self.scene.primary_hits(params, width, height)
 
     def host_world(self):
         """The reference's `world` with its group tree (world.h:48-51), built NOW from the device's tree: shray_device_tree_download +
