@@ -13,6 +13,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 HOST_LIB = os.environ.get("SHRAY_HOST_LIB") or os.path.join(PKG_DIR, "libshray_host.so")
 DIST_LIB = os.path.join(PKG_DIR, "libshray_dist.so")
 QUERY_LIB = os.path.join(PKG_DIR, "libshray_query.so")
+REFIT_LIB = os.path.join(PKG_DIR, "libshray_refit.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
 HIP_LIB = os.environ.get("SHRAY_HIP_LIB") or os.path.join(PKG_DIR, "libshray_hip.so")
 
@@ -259,10 +260,33 @@ QUERY_SYMBOLS = [
     ("shray_primary_hits_device", C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 ]
 
+# include/shader_ray_refit.h ------------------------------------------------------------------------------
+
+
+class RefitInput(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("vertex_count", C.c_int32), ("vertex_stride_floats", C.c_int32),
+                ("normal_offset_floats", C.c_int32), ("vertex_data", C.c_void_p), ("triangle_vertices", C.c_void_p)]
+
+
+class RefitStats(C.Structure):
+    _fields_ = [("sah_cost", C.c_double), ("exact_div_ok", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {"sah_cost": float(self.sah_cost), "exact_div_ok": int(self.exact_div_ok)}
+
+
+REFIT_SYMBOLS = [
+    ("shray_scene_refit", C.c_int, [C.c_void_p, C.POINTER(RefitInput), C.POINTER(RefitStats)]),
+    ("shray_scene_refit_device", C.c_int, [C.c_void_p, C.POINTER(RefitInput), C.POINTER(RefitStats), C.c_void_p]),
+    ("shray_scene_geometry_download", C.c_int, [C.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p]),
+    ("shray_scene_geometry_counts", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+]
+
 _host = None
 _hip = None
 _dist = None
 _query = None
+_refit = None
 
 
 def _bind(lib, table):
@@ -321,6 +345,17 @@ def load_query():
             raise RuntimeError(f"{QUERY_LIB} is not built; run `python __graft_entry__.py build` (or `make -C shader-ray_amd`)")
         _query = _bind(C.CDLL(QUERY_LIB), QUERY_SYMBOLS)
     return _query
+
+
+def load_refit():
+    """Loads the refit library (libshray_refit.so: a client of libshray_hip.so; its errors are read with shray_last_error)."""
+    global _refit
+    if _refit is None:
+        load_hip()
+        if not os.path.exists(REFIT_LIB):
+            raise RuntimeError(f"{REFIT_LIB} is not built; run `python __graft_entry__.py build` (or `make -C shader-ray_amd`)")
+        _refit = _bind(C.CDLL(REFIT_LIB), REFIT_SYMBOLS)
+    return _refit
 
 
 def check_dist(code: int):

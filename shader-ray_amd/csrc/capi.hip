@@ -14,6 +14,7 @@
 
 #include "device_types.h"
 #include "frame_params_defaults.h"
+#include "half_bits.h"
 #include "launch.h"
 #include "packed_layout.h"
 #include "device_tree_internal.h"
@@ -46,33 +47,6 @@ int fail(int code, const char *fmt, ...)
     } while (0)
 
 const float kTerminatorF = 16777215.0f;   // raytracer.es.fs:384
-
-// binary32 -> binary16 bits, round to nearest even (GL_RGB16F upload, ray.cpp:474)
-__host__ __device__ uint16_t float_to_half_bits(float f)
-{
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
-    uint32_t mag = u & 0x7fffffffu;
-    if (mag > 0x7f800000u)
-        return sign | 0x7e00u;                      // NaN
-    if (mag >= 0x477ff000u)
-        return sign | 0x7c00u;                      // overflow -> inf (also inf itself)
-    if (mag < 0x33000001u)
-        return sign;                                // rounds to zero (<= 2^-25)
-    if (mag < 0x38800000u) {                        // subnormal half
-        const int shift = 126 - (int)(mag >> 23);   // 14..24
-        const uint32_t mant = (mag & 0x7fffffu) | 0x800000u;
-        const uint32_t q = mant >> shift;
-        const uint32_t rem = mant & ((1u << shift) - 1u);
-        const uint32_t halfway = 1u << (shift - 1);
-        const uint32_t up = (rem > halfway || (rem == halfway && (q & 1u))) ? 1u : 0u;
-        return sign | (uint16_t)(q + up);
-    }
-    const uint32_t lsb = (mag >> 13) & 1u;
-    mag += 0xfffu + lsb;
-    return sign | (uint16_t)((mag - 0x38000000u) >> 13);
-}
 
 struct DeviceBuffer {
     void *p = nullptr;
@@ -122,6 +96,9 @@ struct shray_scene {
     DeviceBuffer positions, normals16, normals32, boxmin, boxmax, hitmiss, objects;
     DeviceBuffer packed_nodes, packed_tris, pair_nodes;
     uint32_t max_leaf_count = 0;     // the largest leaf: the pair records keep min(count, 127) (packed_layout.h)
+    DeviceBuffer flat_of_packed;     // int32 per packed node: its number in the flattener's arrays (boxmin, boxmax, objects);
+                                     // recorded when packed_ok, for the refit (scene_access_internal.h)
+    std::shared_ptr<void> refit_state;   // what libshray_refit.so keeps for this scene (its level order, scratch): freed with it
     DeviceBuffer env;
     DeviceBuffer counters;
 
@@ -348,11 +325,11 @@ struct TreeBuilder {
         return true;
     }
 
-    // depth-first (negative subtree first) packing
-    void pack(std::vector<PackedNode> &nodes, uint32_t *packed_root)
+    // depth-first (negative subtree first) packing; order[k] = the reference node packed at k
+    void pack(std::vector<PackedNode> &nodes, uint32_t *packed_root, std::vector<uint32_t> &order)
     {
         std::vector<uint32_t> new_index(n, 0);
-        std::vector<uint32_t> order;
+        order.clear();
         order.reserve(n);
         std::vector<char> numbered(n, 0);
         std::vector<uint32_t> todo(1, (uint32_t)d.tree_root);
@@ -930,8 +907,10 @@ int shray_scene_create(const shray_scene_desc *desc, shray_scene **out_scene)
     int depth = 0;
     if (tb.recover_children() && tb.tables_match(&depth)) {
         std::vector<PackedNode> nodes;
+        std::vector<uint32_t> order;
         uint32_t packed_root = 0;
-        tb.pack(nodes, &packed_root);
+        tb.pack(nodes, &packed_root, order);
+        HIP_TRY(s->flat_of_packed.upload(order.data(), order.size() * sizeof(uint32_t)));
         const size_t nt = nv / 3;
         std::vector<PackedTri> tris(nt + 1);   // a spare record: the leaf cache fetches a leaf in 16-byte chunks (leaf_cache.h)
         for (size_t t = 0; t < nt; t++) {
@@ -1276,6 +1255,7 @@ int shray_scene_create_from_device(const shray_device_tree *tree, const shray_de
     HIP_TRY(d_facts.upload(nullptr, sizeof(SceneFromDeviceFacts)));
     HIP_TRY(s->packed_nodes.reserve((size_t)n * 8 * sizeof(PackedNode)));
     HIP_TRY(s->packed_tris.reserve((nt + 1) * sizeof(PackedTri)));
+    HIP_TRY(s->flat_of_packed.copy_of(f.index_of, (size_t)n * sizeof(int)));   // packed order = pre-order: index_of is the map
     const dim3 node_grid((unsigned)((n + block - 1) / block));
     hipLaunchKernelGGL(sd_pack_nodes, node_grid, dim3(block), 0, nullptr, n, t.negative, t.positive, t.start, t.triangles, t.direction, f.index_of,
                        desc.group_boxmin, desc.group_boxmax, (PackedNode *)d_nodes.p, (PackedNode *)s->packed_nodes.p,
@@ -1462,6 +1442,38 @@ int shrayi_scene_query_view(const shray_scene *scene, ShrayQueryScene *out)
     out->packed_ok = scene->packed_ok;
     out->kernel_id = scene->kernel_id;
     out->device = scene->device;
+    return SHRAY_OK;
+}
+
+int shrayi_scene_refit_view(shray_scene *scene, ShrayRefitScene *out)
+{
+    if (!scene || !out)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene is NULL");
+    const SceneView &v = scene->view;
+    out->positions = (float *)scene->positions.p;
+    out->normals32 = (float *)scene->normals32.p;
+    out->normals16 = (uint16_t *)scene->normals16.p;
+    out->boxmin = (float *)scene->boxmin.p;
+    out->boxmax = (float *)scene->boxmax.p;
+    out->packed_nodes = scene->packed_ok ? scene->packed_nodes.p : nullptr;
+    out->packed_tris = scene->packed_ok ? scene->packed_tris.p : nullptr;
+    out->pair_nodes = scene->packed_ok ? scene->pair_nodes.p : nullptr;
+    out->flat_of_packed = scene->packed_ok ? (const int32_t *)scene->flat_of_packed.p : nullptr;
+    out->node_count = v.group_count;
+    out->triangle_count = v.triangle_count;
+    out->packed_root = v.packed_root >> (kNodeShift - kNodeNameShift);
+    out->exact_div_ok = v.exact_div_ok;
+    out->packed_ok = scene->packed_ok;
+    out->device = scene->device;
+    out->state = &scene->refit_state;
+    return SHRAY_OK;
+}
+
+int shrayi_scene_set_exact_div_ok(shray_scene *scene, uint32_t ok)
+{
+    if (!scene)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene is NULL");
+    scene->view.exact_div_ok = ok ? 1u : 0u;
     return SHRAY_OK;
 }
 

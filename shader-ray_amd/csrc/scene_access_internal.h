@@ -1,6 +1,9 @@
 // scene_access_internal.h -- what libshray_query.so (query/) reads of a scene that capi.hip created: the device views the
-// kernels take, and the FrameView a render would build.  Host-only, internal to the two libraries; not part of the C ABI.
+// kernels take, and the FrameView a render would build; and what libshray_refit.so (refit/) rewrites in place.  Host-only,
+// internal to the libraries; not part of the C ABI.
 #pragma once
+
+#include <memory>
 
 #include "device_types.h"
 #include "shader_ray_hip.h"
@@ -16,3 +19,25 @@ struct ShrayQueryScene {
 extern "C" int shrayi_scene_query_view(const shray_scene *scene, ShrayQueryScene *out);
 // shray_render's checks of (params, width, height) at one sample per pixel, then the FrameView it would launch, untiled
 extern "C" int shrayi_frame_view(const shray_frame_params *params, int width, int height, shray::FrameView *out);
+
+// The scene's arrays as the refit rewrites them (include/shader_ray_refit.h): mutable device pointers.  The packed tree's
+// pointers and flat_of_packed are null unless packed_ok.
+struct ShrayRefitScene {
+    float *positions, *normals32;      // 3 floats per corner (reference layout)
+    uint16_t *normals16;               // 3 halves per corner
+    float *boxmin, *boxmax;            // 3 floats per node, the flattener's node numbering
+    void *packed_nodes;                // DeviceNode[8][node_count] (packed_layout.h)
+    void *packed_tris;                 // PackedTri[triangle_count + 1]
+    void *pair_nodes;                  // PackedPair[node_count], or null
+    const int32_t *flat_of_packed;     // [node_count]: packed node k is node flat_of_packed[k] of boxmin / boxmax
+    uint32_t node_count, triangle_count;
+    uint32_t packed_root;              // the root's packed index
+    uint32_t exact_div_ok;
+    bool packed_ok;
+    int device;
+    std::shared_ptr<void> *state;      // the refit library's own per-scene data (level order, scratch); destroyed with the scene
+};
+
+extern "C" int shrayi_scene_refit_view(shray_scene *scene, ShrayRefitScene *out);
+// the host-side flag every launch passes by value (SceneView::exact_div_ok): set after a refit from its new boxes
+extern "C" int shrayi_scene_set_exact_div_ok(shray_scene *scene, uint32_t ok);

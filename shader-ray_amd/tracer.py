@@ -176,6 +176,79 @@ class Scene:
                                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return np.ascontiguousarray(out.cpu().numpy()).view(HIT_DTYPE).reshape(height, width)
 
+    def refit(self, vertex_data, triangle_vertices=None, normal_offset: int | None = None, stream_ptr: int = 0) -> dict:
+        """Refits the scene's BVH to moved vertices (include/shader_ray_refit.h): the tree, the triangle order and every triangle
+        index stay; the corners, boxes and everything derived from them are rewritten in place.  `vertex_data` is [V, stride]
+        float32 (stride >= 3, the position first); `triangle_vertices` [T, 3] int32 vertex indices in the scene's triangle order,
+        or None: `vertex_data` holds the 3 T corners themselves.  `normal_offset`: the column of each vertex's normal, or None to
+        keep the scene's normals.  numpy arrays and CPU tensors take the blocking host path (shray_scene_refit); GPU tensors, which
+        must be on the scene's device, the device path (shray_scene_refit_device) on `stream_ptr` (e.g.
+        torch.cuda.current_stream().cuda_stream), which also returns once the scene is updated.  Returns {"sah_cost", "exact_div_ok"}."""
+        vertex_data, triangle_vertices = _host_if_cpu(vertex_data), _host_if_cpu(triangle_vertices)
+        device = _is_torch(vertex_data)
+        if triangle_vertices is not None and _is_torch(triangle_vertices) != device:
+            raise TypeError("vertex_data and triangle_vertices must both be on the host or both GPU tensors")
+        lib = N.load_refit()
+        corners = C.c_int32()
+        N.check(lib.shray_scene_geometry_counts(self._handle, C.byref(corners), None))
+        if triangle_vertices is not None:
+            count = triangle_vertices.numel() if device else np.size(triangle_vertices)
+            if count != corners.value:
+                raise ValueError(f"triangle_vertices holds {count} indices, the scene has {corners.value} corners (3 per triangle)")
+        if device:
+            here = self.device_index()
+            for name, t in (("vertex_data", vertex_data), ("triangle_vertices", triangle_vertices)):
+                if t is not None and t.device.index != here:
+                    raise ValueError(f"{name} is on {t.device}, the scene on cuda:{here}")
+        inp = N.RefitInput()
+        inp.struct_size = C.sizeof(N.RefitInput)
+        inp.normal_offset_floats = -1 if normal_offset is None else int(normal_offset)
+        keep = []
+        if device:
+            import torch
+            if vertex_data.dtype != torch.float32 or vertex_data.dim() != 2 or not vertex_data.is_contiguous():
+                raise ValueError("vertex_data must be a contiguous float32 [V, stride] tensor")
+            inp.vertex_count, inp.vertex_stride_floats = vertex_data.shape
+            inp.vertex_data = vertex_data.data_ptr()
+            if triangle_vertices is not None:
+                if triangle_vertices.dtype != torch.int32 or not triangle_vertices.is_contiguous():
+                    raise ValueError("triangle_vertices must be a contiguous int32 tensor")
+                inp.triangle_vertices = triangle_vertices.data_ptr()
+        else:
+            vd = np.ascontiguousarray(vertex_data, dtype=np.float32)
+            if vd.ndim != 2:
+                raise ValueError("vertex_data must be [V, stride] float32")
+            inp.vertex_count, inp.vertex_stride_floats = vd.shape
+            inp.vertex_data = vd.ctypes.data
+            keep.append(vd)
+            if triangle_vertices is not None:
+                tv = np.ascontiguousarray(triangle_vertices, dtype=np.int32)
+                inp.triangle_vertices = tv.ctypes.data
+                keep.append(tv)
+        stats = N.RefitStats()
+        if device:
+            N.check(lib.shray_scene_refit_device(self._handle, C.byref(inp), C.byref(stats), C.c_void_p(stream_ptr)))
+        else:
+            N.check(lib.shray_scene_refit(self._handle, C.byref(inp), C.byref(stats)))
+        return stats.as_dict()
+
+    def geometry(self) -> dict:
+        """The scene's reference-layout geometry as it is now (shray_scene_geometry_download): vertex_positions and
+        vertex_normals float32 [corners * 3], group_boxmin and group_boxmax float32 [nodes * 3] (the flattener's numbering)."""
+        lib = N.load_refit()
+        corners, nodes = C.c_int32(), C.c_int32()
+        N.check(lib.shray_scene_geometry_counts(self._handle, C.byref(corners), C.byref(nodes)))
+        out = {"vertex_positions": np.zeros(3 * corners.value, np.float32), "vertex_normals": np.zeros(3 * corners.value, np.float32),
+               "group_boxmin": np.zeros(3 * nodes.value, np.float32), "group_boxmax": np.zeros(3 * nodes.value, np.float32)}
+        N.check(lib.shray_scene_geometry_download(self._handle, *(out[k].ctypes.data_as(N.c_float_p) for k in
+                                                                  ("vertex_positions", "vertex_normals", "group_boxmin", "group_boxmax"))))
+        return out
+
+    def device_index(self) -> int:
+        d = C.c_int()
+        N.check(self._lib.shray_scene_device(self._handle, C.byref(d)))
+        return d.value
+
     def render_batch_into(self, params_list, width: int, height: int, spp: int, out_ptr: int, frame_stride_bytes: int,
                           stream_ptr: int = 0, tiles: N.TileSet | None = None):
         """`len(params_list)` frames in one launch; frame k goes to out_ptr + k * frame_stride_bytes
@@ -186,6 +259,15 @@ class Scene:
             self._handle, array, count, width, height, spp,
             C.byref(tiles) if tiles is not None else None, C.c_void_p(out_ptr), frame_stride_bytes,
             C.c_void_p(stream_ptr)))
+
+
+def _is_torch(a) -> bool:
+    return type(a).__module__.startswith("torch") and hasattr(a, "data_ptr")
+
+
+def _host_if_cpu(a):
+    """a torch tensor in host memory as a numpy array (the host path takes it); anything else as it is"""
+    return a.detach().numpy() if _is_torch(a) and not a.is_cuda else a
 
 
 # a ray buffer / hit array of the query (include/shader_ray_query.h): 32 and 16 bytes per element
@@ -323,6 +405,28 @@ class DeviceWorld:
     def primary_hits(self, params: N.FrameParams, width: int, height: int) -> np.ndarray:
         """Scene.primary_hits on this scene."""
         return self.scene.primary_hits(params, width, height)
+
+    def refit(self, vertex_data, stream_ptr: int | None = None) -> dict:
+        """Refits the scene to moved vertices (Scene.refit): `vertex_data` is [V, 3] or [V, 9] float32 (numpy, or a torch tensor on
+        the scene's device), in the numbering of the loaded triangle set (shray_host_triangles); with 9 columns (geometry.h:34-38)
+        the normals are taken from column 6, with 3 the scene's normals are kept.  The tree's post-build triangle_vertices are
+        uploaded once and reused.  Runs on `stream_ptr` (default: torch's current stream).  frame_params() stays framed on the
+        mesh as loaded, and flat_arrays() and host_world() keep describing the loaded mesh."""
+        import torch
+        if getattr(self, "_d_triangle_vertices", None) is None:
+            tree = N.TreeDesc()
+            N.check(self._hip.shray_device_tree_download(self._tree, C.byref(tree), None))
+            tv = np.ctypeslib.as_array(tree.triangle_vertices, shape=(3 * tree.triangle_count,)).copy() if tree.triangle_count else \
+                np.zeros(0, np.int32)
+            self._d_triangle_vertices = torch.from_numpy(tv).to(torch.device("cuda", self.scene.device_index()))
+        d = self._d_triangle_vertices.device
+        vd = vertex_data if _is_torch(vertex_data) else torch.from_numpy(np.ascontiguousarray(vertex_data, dtype=np.float32))
+        vd = vd.to(device=d, dtype=torch.float32).contiguous()
+        if vd.dim() != 2 or vd.shape[1] not in (3, 9):
+            raise ValueError("vertex_data must be [V, 3] or [V, 9] float32")
+        if stream_ptr is None:
+            stream_ptr = torch.cuda.current_stream(d).cuda_stream
+        return self.scene.refit(vd, self._d_triangle_vertices, 6 if vd.shape[1] == 9 else None, stream_ptr)
 
     def host_world(self):
         """The reference's `world` with its group tree (world.h:48-51), built NOW from the device's tree: shray_device_tree_download +
