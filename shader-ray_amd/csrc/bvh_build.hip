@@ -36,9 +36,8 @@
 #include <vector>
 
 #include "device_tree_internal.h"
+#include "error_internal.h"
 #include "shader_ray_hip.h"
-
-extern "C" int shrayi_fail(int code, const char *message);   // capi.hip: sets shray_last_error()
 
 namespace {
 
@@ -576,14 +575,12 @@ struct shray_device_tree {
     double seconds = 0;
 };
 
-#define BVH_TRY(expr)                                                                                     \
-    do {                                                                                                  \
-        const hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) {                                                                           \
-            char text_[256];                                                                              \
-            snprintf(text_, sizeof text_, "shray_bvh_build_device: %s failed: %s", #expr, hipGetErrorString(e_)); \
-            return shrayi_fail(SHRAY_ERR_DEVICE, text_);                                                  \
-        }                                                                                                 \
+// (every HIP error, out-of-memory included, is SHRAY_ERR_DEVICE here)
+#define BVH_TRY(expr)                                                                                                  \
+    do {                                                                                                               \
+        const hipError_t e_ = (expr);                                                                                  \
+        if (e_ != hipSuccess)                                                                                          \
+            return fail(SHRAY_ERR_DEVICE, "shray_bvh_build_device: %s failed: %s", #expr, hipGetErrorString(e_));     \
     } while (0)
 
 extern "C" {

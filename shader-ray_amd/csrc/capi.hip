@@ -5,14 +5,13 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "device_types.h"
+#include "error_internal.h"
 #include "frame_params_defaults.h"
 #include "half_bits.h"
 #include "launch.h"
@@ -26,25 +25,6 @@ using namespace shray;
 namespace {
 
 thread_local std::string g_error;
-
-int fail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_error = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(e_ == hipErrorOutOfMemory ? SHRAY_ERR_OUT_OF_MEMORY : SHRAY_ERR_DEVICE, \
-                        "%s failed: %s", #expr, hipGetErrorString(e_));                        \
-    } while (0)
 
 const float kTerminatorF = 16777215.0f;   // raytracer.es.fs:384
 
@@ -200,8 +180,13 @@ struct shray_scene {
 
 namespace {
 
-// Validation + reconstruction of the tree from the eight (hit, miss) tables.
-// On success fills `nodes` (packed, depth-first) and the depth.
+// host copies of a tree's pre-order arrays (TreeBuilder::preorder)
+struct PreorderTree {
+    std::vector<int32_t> negative, positive, start, triangles, index_of;
+    std::vector<float> direction;
+};
+
+// Validation + reconstruction of the tree from the eight (hit, miss) tables, and its pre-order arrays.
 struct TreeBuilder {
     const shray_scene_desc &d;
     uint32_t n, stride, tri_count;
@@ -325,41 +310,34 @@ struct TreeBuilder {
         return true;
     }
 
-    // depth-first (negative subtree first) packing; order[k] = the reference node packed at k
-    void pack(std::vector<PackedNode> &nodes, uint32_t *packed_root, std::vector<uint32_t> &order)
+    // The tree as ShrayDeviceTreeView holds it: pre-order (a node, its negative subtree, its positive subtree; the root at 0),
+    // a branch's children as pre-order indices and its split direction as the unit vector of its axis, a leaf's (start,
+    // count), and index_of[k] = the reference node at k.  Pre-order is the packed order (packed_layout.h).
+    void preorder(PreorderTree &t) const
     {
-        std::vector<uint32_t> new_index(n, 0);
-        order.clear();
-        order.reserve(n);
-        std::vector<char> numbered(n, 0);
-        std::vector<uint32_t> todo(1, (uint32_t)d.tree_root);
+        t.negative.assign(n, -1);
+        t.positive.assign(n, -1);
+        t.start.assign(n, 0);
+        t.triangles.assign(n, 0);
+        t.direction.assign(3 * (size_t)n, 0.0f);
+        // (a node, where its parent names it): a node is numbered when it is taken, its negative subtree is taken next
+        std::vector<std::pair<uint32_t, int32_t *>> todo(1, {(uint32_t)d.tree_root, nullptr});
         while (!todo.empty()) {
-            const uint32_t g = todo.back();
+            const auto [g, named_at] = todo.back();
             todo.pop_back();
-            if (!numbered[g]) {
-                new_index[g] = (uint32_t)order.size();
-                order.push_back(g);
-            }
+            const int32_t k = (int32_t)t.index_of.size();
+            t.index_of.push_back((int32_t)g);
+            if (named_at)
+                *named_at = k;
             if (neg[g] >= 0) {
-                todo.push_back((uint32_t)pos[g]);
-                todo.push_back((uint32_t)neg[g]);
-            }
-        }
-        nodes.resize(n);
-        for (uint32_t k = 0; k < n; k++) {
-            const uint32_t g = order[k];
-            PackedNode &pn = nodes[k];
-            memcpy(pn.lo, d.group_boxmin + 3 * (size_t)g, 12);
-            memcpy(pn.hi, d.group_boxmax + 3 * (size_t)g, 12);
-            if (neg[g] >= 0) {
-                pn.a = ((uint32_t)axis[g] << 30) | new_index[pos[g]];
-                pn.b = new_index[neg[g]];
+                t.direction[3 * (size_t)k + axis[g]] = 1.0f;
+                todo.push_back({(uint32_t)pos[g], &t.positive[k]});
+                todo.push_back({(uint32_t)neg[g], &t.negative[k]});
             } else {
-                pn.a = (uint32_t)d.group_objects[2 * (size_t)g];
-                pn.b = kLeafFlag | (uint32_t)d.group_objects[2 * (size_t)g + 1];
+                t.start[k] = (int32_t)d.group_objects[2 * (size_t)g];
+                t.triangles[k] = (int32_t)d.group_objects[2 * (size_t)g + 1];
             }
         }
-        *packed_root = new_index[(uint32_t)d.tree_root];
     }
 };
 
@@ -812,8 +790,12 @@ int launch(shray_scene *s, const FrameView &fr_in, float4 *d_out, DeviceCounters
 
 }   // namespace
 
-// error reporting for the library's other translation units (flatten.hip)
-extern "C" int shrayi_fail(int code, const char *message) { return fail(code, "%s", message); }
+// every error of the library and of its clients (error_internal.h) ends here
+extern "C" int shrayi_fail(int code, const char *message)
+{
+    g_error = message;
+    return code;
+}
 
 extern "C" {
 
@@ -851,208 +833,15 @@ void shray_frame_params_init(shray_frame_params *params)
         shray_frame_params_defaults(params);
 }
 
-int shray_scene_create(const shray_scene_desc *desc, shray_scene **out_scene)
-{
-    if (!desc || !out_scene)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "desc or out_scene is NULL");
-    *out_scene = nullptr;
-    if (desc->struct_size != sizeof(shray_scene_desc))
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "shray_scene_desc.struct_size is %u, this library expects %zu",
-                    desc->struct_size, sizeof(shray_scene_desc));
-    if (desc->data_texture_width == 0 || desc->group_count < 1 || desc->group_data_rows < 1 ||
-        desc->tree_root < 0 || desc->tree_root >= desc->group_count || desc->vertex_count % 3 != 0)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "inconsistent counts (width %u, %d nodes in %d rows, root %d, %u vertices)",
-                    desc->data_texture_width, desc->group_count, desc->group_data_rows, desc->tree_root,
-                    desc->vertex_count);
-    const uint64_t stride = (uint64_t)desc->data_texture_width * (uint64_t)desc->group_data_rows;
-    const uint64_t vertex_texels = (uint64_t)desc->data_texture_width * (uint64_t)desc->vertex_data_rows;
-    if ((uint64_t)desc->group_count > stride || desc->vertex_count > vertex_texels)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "counts exceed width * rows");
-    if (!desc->group_boxmin || !desc->group_boxmax || !desc->group_hitmiss || !desc->group_objects ||
-        (desc->vertex_count && (!desc->vertex_positions || !desc->vertex_normals)))
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "a required array is NULL");
-    // The shader carries every index as float32 (raytracer.es.fs:239-245, :384):
-    // exact only below 2^24, and node links at or above 16777215 mean "stop".
-    if (stride * 8 > 16777216ull || desc->vertex_count > 16777216u)
-        return fail(SHRAY_ERR_INDEX_RANGE, "scene too large for float32 indices (%llu link texels, %u vertices; "
-                    "limit 2^24)", (unsigned long long)(stride * 8), desc->vertex_count);
-
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess)
-        return fail(SHRAY_ERR_NO_DEVICE, "no HIP device is available (hipGetDevice failed)");
-
-    TreeBuilder tb(*desc);
-    if (!tb.links_are_safe())
-        return fail(SHRAY_ERR_BAD_TREE, "%s", tb.why.c_str());
-
-    std::unique_ptr<shray_scene> s(new shray_scene);
-    s->device = device;
-    const size_t nv = desc->vertex_count, ng = (size_t)desc->group_count;
-
-    HIP_TRY(s->positions.upload(desc->vertex_positions, nv * 12));
-    HIP_TRY(s->normals32.upload(desc->vertex_normals, nv * 12));
-    {
-        std::vector<uint16_t> halves(nv * 3);
-        for (size_t k = 0; k < halves.size(); k++)
-            halves[k] = float_to_half_bits(desc->vertex_normals[k]);
-        HIP_TRY(s->normals16.upload(halves.data(), halves.size() * 2));
-    }
-    HIP_TRY(s->boxmin.upload(desc->group_boxmin, ng * 12));
-    HIP_TRY(s->boxmax.upload(desc->group_boxmax, ng * 12));
-    HIP_TRY(s->objects.upload(desc->group_objects, ng * 8));
-    HIP_TRY(s->hitmiss.upload(desc->group_hitmiss, (size_t)stride * 8 * 8));
-    HIP_TRY(s->counters.upload(nullptr, sizeof(DeviceCounters) * kCounterShards));
-
-    // packed layout for the stack kernel, if the tables describe a canonical threaded tree
-    int depth = 0;
-    if (tb.recover_children() && tb.tables_match(&depth)) {
-        std::vector<PackedNode> nodes;
-        std::vector<uint32_t> order;
-        uint32_t packed_root = 0;
-        tb.pack(nodes, &packed_root, order);
-        HIP_TRY(s->flat_of_packed.upload(order.data(), order.size() * sizeof(uint32_t)));
-        const size_t nt = nv / 3;
-        std::vector<PackedTri> tris(nt + 1);   // a spare record: the leaf cache fetches a leaf in 16-byte chunks (leaf_cache.h)
-        for (size_t t = 0; t < nt; t++) {
-            const float *v = desc->vertex_positions + 9 * t;
-            PackedTri &pt = tris[t];
-            memset(&pt, 0, sizeof(pt));
-            for (int a = 0; a < 3; a++) {
-                pt.v0[a] = v[a];
-                pt.e0[a] = v[3 + a] - v[a];        // e0 = v1 - v0, raytracer.es.fs:304
-                pt.e1[a] = v[a] - v[6 + a];        // e1 = v0 - v2, raytracer.es.fs:305
-            }
-        }
-        {
-            // the device's form (packed_layout.h): one copy per direction octant, holding a box as the planes a ray of that
-            // octant enters and leaves it by and a branch's children in the order it visits them, named by byte offset / 8
-            // (2^21 nodes at most -- the float32-index check above -- so the eight copies end below 2^29 bytes)
-            const size_t n = nodes.size();
-            std::vector<PackedNode> copies(n * 8);
-            for (uint32_t o = 0; o < 8; o++) {
-                PackedNode *c = copies.data() + (size_t)o * n;
-                for (size_t k = 0; k < n; k++) {
-                    PackedNode pn = nodes[k];
-                    for (int axis = 0; axis < 3; axis++)
-                        if (!((o >> axis) & 1u))
-                            std::swap(pn.lo[axis], pn.hi[axis]);
-                    if (!(pn.b & kLeafFlag)) {
-                        const uint32_t axis = pn.a >> 30, pos = (pn.a & kChildMask) << (kNodeShift - kNodeNameShift),
-                                       neg = pn.b << (kNodeShift - kNodeNameShift);
-                        const bool negative_first = (o >> axis) & 1u;     // D[axis] > 0 (a zero component: visit_decision)
-                        pn.a = (1u << (kAxisHotShift + axis)) | (negative_first ? neg : pos);
-                        pn.b = negative_first ? pos : neg;
-                    }
-                    // the record's words in the order the visit's packed arithmetic wants them in its register pairs
-                    // (packed_layout.h: DeviceNode): { entry.x, entry.y, exit.x, exit.y } { entry.z, exit.z, a, b }
-                    DeviceNode dn;
-                    dn.entry_xy[0] = pn.lo[0];
-                    dn.entry_xy[1] = pn.lo[1];
-                    dn.exit_xy[0] = pn.hi[0];
-                    dn.exit_xy[1] = pn.hi[1];
-                    dn.z[0] = pn.lo[2];
-                    dn.z[1] = pn.hi[2];
-                    dn.a = pn.a;
-                    dn.b = pn.b;
-                    memcpy(&c[k], &dn, sizeof(dn));
-                }
-            }
-            HIP_TRY(s->packed_nodes.upload(copies.data(), copies.size() * sizeof(PackedNode)));
-            s->view.packed_nodes_bytes = (uint32_t)(n * sizeof(PackedNode));
-        }
-        HIP_TRY(s->packed_tris.upload(tris.data(), tris.size() * sizeof(PackedTri)));
-        s->view.packed_root = packed_root << (kNodeShift - kNodeNameShift);
-        // sibling pairs for the pair traversal: the record of an inner node holds both children's boxes and links.
-        // A pair link keeps the child index in kPairIndexMask's 22 bits.  The float32-index check above already bounds
-        // a scene at 2^21 nodes (8 link tables x stride <= 2^24); a tree that ever got past that keeps no pair records,
-        // so pair_policy() answers false and kernel 3 runs the one-visit instances.
-        if (nodes.size() <= (size_t)kPairIndexMask + 1) {
-            std::vector<PackedPair> pairs(nodes.size());
-            memset(pairs.data(), 0, pairs.size() * sizeof(PackedPair));
-            uint32_t largest = 0;
-            auto link_of = [&](uint32_t child, uint32_t *info) {
-                const PackedNode &c = nodes[child];
-                if (c.b & kLeafFlag) {
-                    const uint32_t count = c.b & ~kLeafFlag;
-                    largest = std::max(largest, count);
-                    *info = c.a;
-                    return child | (std::min(count, kPairCountMask) << kPairCountShift) | kLeafFlag;
-                }
-                *info = 0;
-                return child | ((c.a >> 30) << kPairAxisShift);
-            };
-            for (size_t k = 0; k < nodes.size(); k++) {
-                const PackedNode &pn = nodes[k];
-                if (pn.b & kLeafFlag) {
-                    largest = std::max(largest, pn.b & ~kLeafFlag);
-                    continue;
-                }
-                const uint32_t pos = pn.a & kChildMask, neg = pn.b;
-                PackedPair &pp = pairs[k];
-                memcpy(pp.lo0, nodes[neg].lo, 12);
-                memcpy(pp.hi0, nodes[neg].hi, 12);
-                pp.link0 = link_of(neg, &pp.info0);
-                memcpy(pp.lo1, nodes[pos].lo, 12);
-                memcpy(pp.hi1, nodes[pos].hi, 12);
-                pp.link1 = link_of(pos, &pp.info1);
-            }
-            HIP_TRY(s->pair_nodes.upload(pairs.data(), pairs.size() * sizeof(PackedPair)));
-            s->max_leaf_count = largest;
-            uint32_t dummy = 0;
-            s->view.pair_root_link = link_of(packed_root, &dummy);
-            uint32_t bits = 1;
-            while ((1ull << bits) < nodes.size())
-                bits++;
-            s->view.pair_index_bits = bits;
-        }
-        // operand-range condition of exact_div.h on the scene's side: every box coordinate
-        // is zero or has magnitude in [2^-70, 2^60)
-        bool coords_ok = true;
-        for (const PackedNode &pn : nodes) {
-            for (int k = 0; k < 3 && coords_ok; k++) {
-                for (float c : {pn.lo[k], pn.hi[k]}) {
-                    const float m = fabsf(c);
-                    if (!(c == 0.0f || (m >= 0x1p-70f && m < 0x1p60f)))
-                        coords_ok = false;
-                }
-            }
-        }
-        s->view.exact_div_ok = coords_ok ? 1u : 0u;
-        s->stack_levels = std::max(3, depth);   // at least three: the convergent driver stages a round of samples through levels 0-2
-        s->packed_ok = true;
-    }
-
-    SceneView &v = s->view;
-    v.positions = (const float *)s->positions.p;
-    v.normals16 = (const uint16_t *)s->normals16.p;
-    v.normals32 = (const float *)s->normals32.p;
-    v.boxmin = (const float *)s->boxmin.p;
-    v.boxmax = (const float *)s->boxmax.p;
-    v.hitmiss = (const float *)s->hitmiss.p;
-    v.objects = (const float *)s->objects.p;
-    v.table_stride = (uint32_t)stride;
-    v.group_count = (uint32_t)ng;
-    v.triangle_count = (uint32_t)(nv / 3);
-    v.tree_root = (float)desc->tree_root;
-    v.packed_nodes = s->packed_nodes.p;
-    v.packed_tris = s->packed_tris.p;
-    v.pair_nodes = s->pair_nodes.p;
-    v.env = nullptr;
-    v.env_w = v.env_h = 0;
-
-    *out_scene = s.release();
-    return SHRAY_OK;
-}
-
-// ---- the same scene from a tree that never left the device ----------------------------------------------------------------
-// shray_bvh_build_device -> shray_flatten_device_tree -> here (round 6; SURVEY 8(f) rank 3: scene turnaround,
-// world.cpp:46-134, :298-347; bvh.cpp:288-358).  shray_scene_create takes the reference's arrays from the HOST, proves that the
-// eight (hit, miss) tables are one threaded binary tree (TreeBuilder) and derives the packed tree, its eight octant copies, the
-// packed triangles, the pair records and the fp16 normals on the host.  Here the tree exists as arrays already -- the tables were
-// threaded FROM it, by flatten.hip, so there is nothing to recover --, and everything derived from it is computed where it lies:
-// one thread per node / triangle / corner.  Packed order = the tree's pre-order (TreeBuilder::pack walks the same way: a node,
-// its negative subtree, its positive subtree).  The arrays equal shray_scene_create's bit for bit (tests/test_gpu_scene_device.py
-// reads both back).
+// ---- scene creation ---------------------------------------------------------------------------------------------------------
+// Two ways in.  shray_scene_create takes the reference's arrays from the HOST and proves that the eight (hit, miss) tables are one
+// threaded binary tree (TreeBuilder).  shray_scene_create_from_device takes a tree that never left the device --
+// shray_bvh_build_device -> shray_flatten_device_tree -> here (round 6; SURVEY 8(f) rank 3: scene turnaround, world.cpp:46-134,
+// :298-347; bvh.cpp:288-358) --, whose tables were threaded FROM it by flatten.hip, so there is nothing to recover.  Either way the
+// tree reaches derive_arrays as pre-order arrays on the device, and everything derived from it is computed there: one thread per
+// node / triangle / corner.  Packed order = the tree's pre-order (a node, its negative subtree, its positive subtree).
+// tests/test_gpu_scene_device.py reads the arrays of both paths back and compares them with each other and with a numpy
+// restatement (tests/scene_ref.py).
 namespace {
 
 struct SceneFromDeviceFacts {     // what the kernels report back: 16 bytes, one copy
@@ -1205,65 +994,58 @@ __global__ void sd_pair_records(int n, const PackedNode *__restrict__ nodes, Pac
     pairs[k] = pp;
 }
 
-}   // namespace
 
-int shray_scene_create_from_device(const shray_device_tree *tree, const shray_device_flat *flat, shray_scene **out_scene)
+// The shader carries every index as float32 (raytracer.es.fs:239-245, :384): exact only below 2^24, and node links at or above
+// 16777215 mean "stop".
+int check_index_range(const shray_scene_desc &d)
 {
-    if (!tree || !flat || !out_scene)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "tree, flat or out_scene is NULL");
-    *out_scene = nullptr;
-    ShrayDeviceTreeView t;
-    ShrayDeviceFlatView f;
-    if (const int rc = shrayi_device_tree_view(tree, &t))
-        return rc;
-    if (const int rc = shrayi_device_flat_view(flat, &f))
-        return rc;
-    const shray_scene_desc &desc = f.desc;
-    if (desc.group_count != t.node_count || desc.vertex_count != 3u * (uint32_t)t.triangle_count || !f.index_of)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "the flattened arrays are not those of this tree (%d nodes / %d, %u corners / %d triangles)",
-                    desc.group_count, t.node_count, desc.vertex_count, t.triangle_count);
-    const uint64_t stride = (uint64_t)desc.data_texture_width * (uint64_t)desc.group_data_rows;
-    // the shader's float32 indices (shray_scene_create)
-    if (stride * 8 > 16777216ull || desc.vertex_count > 16777216u)
+    const uint64_t stride = (uint64_t)d.data_texture_width * (uint64_t)d.group_data_rows;
+    if (stride * 8 > 16777216ull || d.vertex_count > 16777216u)
         return fail(SHRAY_ERR_INDEX_RANGE, "scene too large for float32 indices (%llu link texels, %u vertices; limit 2^24)",
-                    (unsigned long long)(stride * 8), desc.vertex_count);
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess)
-        return fail(SHRAY_ERR_NO_DEVICE, "no HIP device is available (hipGetDevice failed)");
+                    (unsigned long long)(stride * 8), d.vertex_count);
+    return SHRAY_OK;
+}
 
-    std::unique_ptr<shray_scene> s(new shray_scene);
-    s->device = device;
-    const size_t nv = desc.vertex_count, ng = (size_t)desc.group_count, nt = nv / 3;
-    const int n = t.node_count, block = 256;
-
-    // the reference's arrays (the literal kernel's inputs): copies on the device
-    HIP_TRY(s->positions.copy_of(desc.vertex_positions, nv * 12));
-    HIP_TRY(s->normals32.copy_of(desc.vertex_normals, nv * 12));
-    HIP_TRY(s->boxmin.copy_of(desc.group_boxmin, ng * 12));
-    HIP_TRY(s->boxmax.copy_of(desc.group_boxmax, ng * 12));
-    HIP_TRY(s->objects.copy_of(desc.group_objects, ng * 8));
-    HIP_TRY(s->hitmiss.copy_of(desc.group_hitmiss, (size_t)stride * 8 * 8));
-    HIP_TRY(s->counters.upload(nullptr, sizeof(DeviceCounters) * kCounterShards));
-    HIP_TRY(s->normals16.reserve(nv * 3 * 2));
-    if (nv)
-        hipLaunchKernelGGL(sd_half_normals, dim3((unsigned)((nv * 3 + block - 1) / block)), dim3(block), 0, nullptr, nv * 3,
+// What a scene derives from the reference's arrays already in it (positions, normals32, and boxmin / boxmax in the flattener's
+// node numbering), on the null stream; returns when every array is complete.  Every scene gets the fp16 normals: the literal
+// kernel reads them.  Given `tree` -- pre-order arrays in device memory, ShrayDeviceTreeView's form, with index_of[k] the
+// flattener's number of node k -- it also gets the packed layout the stack kernel runs on (packed_layout.h): the eight octant
+// copies, the packed triangles, the pair records and the facts read back with them.  `depth`: the deepest ray stack if the
+// caller knows it, -1 to count it from tree->parent.
+int derive_arrays(shray_scene *s, size_t corners, const ShrayDeviceTreeView *tree, const int *index_of, int depth)
+{
+    const int block = 256;
+    HIP_TRY(s->normals16.reserve(corners * 3 * 2));
+    if (corners)
+        hipLaunchKernelGGL(sd_half_normals, dim3((unsigned)((corners * 3 + block - 1) / block)), dim3(block), 0, nullptr, corners * 3,
                            (const float *)s->normals32.p, (uint16_t *)s->normals16.p);
+    if (!tree) {
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return SHRAY_OK;
+    }
 
     // the packed tree, its octant copies, the packed triangles, the pair records
+    const int n = tree->node_count;
+    const size_t nt = corners / 3;
     DeviceBuffer d_nodes, d_facts;
     HIP_TRY(d_nodes.reserve((size_t)n * sizeof(PackedNode)));
     HIP_TRY(d_facts.upload(nullptr, sizeof(SceneFromDeviceFacts)));
     HIP_TRY(s->packed_nodes.reserve((size_t)n * 8 * sizeof(PackedNode)));
     HIP_TRY(s->packed_tris.reserve((nt + 1) * sizeof(PackedTri)));
-    HIP_TRY(s->flat_of_packed.copy_of(f.index_of, (size_t)n * sizeof(int)));   // packed order = pre-order: index_of is the map
+    HIP_TRY(s->flat_of_packed.copy_of(index_of, (size_t)n * sizeof(int)));   // packed order = pre-order: index_of is the map
     const dim3 node_grid((unsigned)((n + block - 1) / block));
-    hipLaunchKernelGGL(sd_pack_nodes, node_grid, dim3(block), 0, nullptr, n, t.negative, t.positive, t.start, t.triangles, t.direction, f.index_of,
-                       desc.group_boxmin, desc.group_boxmax, (PackedNode *)d_nodes.p, (PackedNode *)s->packed_nodes.p,
-                       (SceneFromDeviceFacts *)d_facts.p);
-    hipLaunchKernelGGL(sd_stack_depth, node_grid, dim3(block), 0, nullptr, n, t.parent, t.negative, (const PackedNode *)d_nodes.p,
-                       (SceneFromDeviceFacts *)d_facts.p);
+    hipLaunchKernelGGL(sd_pack_nodes, node_grid, dim3(block), 0, nullptr, n, tree->negative, tree->positive, tree->start, tree->triangles,
+                       tree->direction, index_of, (const float *)s->boxmin.p, (const float *)s->boxmax.p, (PackedNode *)d_nodes.p,
+                       (PackedNode *)s->packed_nodes.p, (SceneFromDeviceFacts *)d_facts.p);
+    if (depth < 0)
+        hipLaunchKernelGGL(sd_stack_depth, node_grid, dim3(block), 0, nullptr, n, tree->parent, tree->negative, (const PackedNode *)d_nodes.p,
+                           (SceneFromDeviceFacts *)d_facts.p);
     hipLaunchKernelGGL(sd_pack_triangles, dim3((unsigned)((nt + 1 + block - 1) / block)), dim3(block), 0, nullptr, nt,
                        (const float *)s->positions.p, (PackedTri *)s->packed_tris.p);
+    // A pair link keeps the child index in kPairIndexMask's 22 bits.  The float32-index check bounds a scene at 2^21 nodes
+    // (8 link tables x stride <= 2^24); a tree that ever got past that keeps no pair records, so pair_policy() answers false
+    // and kernel 3 runs the one-visit instances.
     const bool pairs = (size_t)n <= (size_t)kPairIndexMask + 1;
     if (pairs) {
         HIP_TRY(s->pair_nodes.reserve((size_t)n * sizeof(PackedPair)));
@@ -1272,7 +1054,7 @@ int shray_scene_create_from_device(const shray_device_tree *tree, const shray_de
     HIP_TRY(hipGetLastError());
     SceneFromDeviceFacts facts;
     HIP_TRY(hipMemcpy(&facts, d_facts.p, sizeof(facts), hipMemcpyDeviceToHost));   // (waits for the kernels and copies above)
-    if (facts.not_canonical)
+    if (facts.not_canonical)    // (only a device tree can: the host path's directions are unit axis vectors)
         return fail(SHRAY_ERR_BAD_TREE, "a split direction of the device tree is not a positive unit axis vector: take the host path "
                                         "(shray_device_tree_download, shray_scene_create)");
     s->view.packed_nodes_bytes = (uint32_t)((size_t)n * sizeof(PackedNode));
@@ -1290,9 +1072,15 @@ int shray_scene_create_from_device(const shray_device_tree *tree, const shray_de
         s->view.pair_index_bits = bits;
     }
     s->view.exact_div_ok = facts.coords_out_of_range ? 0u : 1u;
-    s->stack_levels = std::max(3, facts.depth);
+    // at least three: the convergent driver stages a round of samples through levels 0-2
+    s->stack_levels = std::max(3, depth < 0 ? facts.depth : depth);
     s->packed_ok = true;
+    return SHRAY_OK;
+}
 
+// the scene's arrays as every launch takes them (the packed layout's facts are derive_arrays')
+void fill_view(shray_scene *s, const shray_scene_desc &desc)
+{
     SceneView &v = s->view;
     v.positions = (const float *)s->positions.p;
     v.normals16 = (const uint16_t *)s->normals16.p;
@@ -1301,15 +1089,127 @@ int shray_scene_create_from_device(const shray_device_tree *tree, const shray_de
     v.boxmax = (const float *)s->boxmax.p;
     v.hitmiss = (const float *)s->hitmiss.p;
     v.objects = (const float *)s->objects.p;
-    v.table_stride = (uint32_t)stride;
-    v.group_count = (uint32_t)ng;
-    v.triangle_count = (uint32_t)nt;
+    v.table_stride = desc.data_texture_width * (uint32_t)desc.group_data_rows;
+    v.group_count = (uint32_t)desc.group_count;
+    v.triangle_count = desc.vertex_count / 3;
     v.tree_root = (float)desc.tree_root;
     v.packed_nodes = s->packed_nodes.p;
     v.packed_tris = s->packed_tris.p;
     v.pair_nodes = s->pair_nodes.p;
     v.env = nullptr;
     v.env_w = v.env_h = 0;
+}
+
+}   // namespace
+
+int shray_scene_create(const shray_scene_desc *desc, shray_scene **out_scene)
+{
+    if (!desc || !out_scene)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "desc or out_scene is NULL");
+    *out_scene = nullptr;
+    if (desc->struct_size != sizeof(shray_scene_desc))
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "shray_scene_desc.struct_size is %u, this library expects %zu",
+                    desc->struct_size, sizeof(shray_scene_desc));
+    if (desc->data_texture_width == 0 || desc->group_count < 1 || desc->group_data_rows < 1 ||
+        desc->tree_root < 0 || desc->tree_root >= desc->group_count || desc->vertex_count % 3 != 0)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "inconsistent counts (width %u, %d nodes in %d rows, root %d, %u vertices)",
+                    desc->data_texture_width, desc->group_count, desc->group_data_rows, desc->tree_root,
+                    desc->vertex_count);
+    const uint64_t stride = (uint64_t)desc->data_texture_width * (uint64_t)desc->group_data_rows;
+    const uint64_t vertex_texels = (uint64_t)desc->data_texture_width * (uint64_t)desc->vertex_data_rows;
+    if ((uint64_t)desc->group_count > stride || desc->vertex_count > vertex_texels)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "counts exceed width * rows");
+    if (!desc->group_boxmin || !desc->group_boxmax || !desc->group_hitmiss || !desc->group_objects ||
+        (desc->vertex_count && (!desc->vertex_positions || !desc->vertex_normals)))
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "a required array is NULL");
+    if (const int rc = check_index_range(*desc))
+        return rc;
+
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess)
+        return fail(SHRAY_ERR_NO_DEVICE, "no HIP device is available (hipGetDevice failed)");
+
+    TreeBuilder tb(*desc);
+    if (!tb.links_are_safe())
+        return fail(SHRAY_ERR_BAD_TREE, "%s", tb.why.c_str());
+
+    std::unique_ptr<shray_scene> s(new shray_scene);
+    s->device = device;
+    const size_t nv = desc->vertex_count, ng = (size_t)desc->group_count;
+
+    HIP_TRY(s->positions.upload(desc->vertex_positions, nv * 12));
+    HIP_TRY(s->normals32.upload(desc->vertex_normals, nv * 12));
+    HIP_TRY(s->boxmin.upload(desc->group_boxmin, ng * 12));
+    HIP_TRY(s->boxmax.upload(desc->group_boxmax, ng * 12));
+    HIP_TRY(s->objects.upload(desc->group_objects, ng * 8));
+    HIP_TRY(s->hitmiss.upload(desc->group_hitmiss, (size_t)stride * 8 * 8));
+    HIP_TRY(s->counters.upload(nullptr, sizeof(DeviceCounters) * kCounterShards));
+
+    // the packed layout for the stack kernel, if the tables describe a canonical threaded tree: its pre-order arrays, on the device
+    int depth = 0;
+    const bool canonical = tb.recover_children() && tb.tables_match(&depth);
+    ShrayDeviceTreeView t{};
+    DeviceBuffer negative, positive, start, triangles, direction, index_of;
+    if (canonical) {
+        PreorderTree pre;
+        tb.preorder(pre);
+        HIP_TRY(negative.upload(pre.negative.data(), ng * 4));
+        HIP_TRY(positive.upload(pre.positive.data(), ng * 4));
+        HIP_TRY(start.upload(pre.start.data(), ng * 4));
+        HIP_TRY(triangles.upload(pre.triangles.data(), ng * 4));
+        HIP_TRY(direction.upload(pre.direction.data(), ng * 12));
+        HIP_TRY(index_of.upload(pre.index_of.data(), ng * 4));
+        t.node_count = (int)ng;
+        t.negative = (const int *)negative.p;
+        t.positive = (const int *)positive.p;
+        t.start = (const int *)start.p;
+        t.triangles = (const int *)triangles.p;
+        t.direction = (const float *)direction.p;
+    }
+    if (const int rc = derive_arrays(s.get(), nv, canonical ? &t : nullptr, (const int *)index_of.p, depth))
+        return rc;
+    fill_view(s.get(), *desc);
+    *out_scene = s.release();
+    return SHRAY_OK;
+}
+
+int shray_scene_create_from_device(const shray_device_tree *tree, const shray_device_flat *flat, shray_scene **out_scene)
+{
+    if (!tree || !flat || !out_scene)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "tree, flat or out_scene is NULL");
+    *out_scene = nullptr;
+    ShrayDeviceTreeView t;
+    ShrayDeviceFlatView f;
+    if (const int rc = shrayi_device_tree_view(tree, &t))
+        return rc;
+    if (const int rc = shrayi_device_flat_view(flat, &f))
+        return rc;
+    const shray_scene_desc &desc = f.desc;
+    if (desc.group_count != t.node_count || desc.vertex_count != 3u * (uint32_t)t.triangle_count || !f.index_of)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "the flattened arrays are not those of this tree (%d nodes / %d, %u corners / %d triangles)",
+                    desc.group_count, t.node_count, desc.vertex_count, t.triangle_count);
+    if (const int rc = check_index_range(desc))
+        return rc;
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess)
+        return fail(SHRAY_ERR_NO_DEVICE, "no HIP device is available (hipGetDevice failed)");
+
+    std::unique_ptr<shray_scene> s(new shray_scene);
+    s->device = device;
+    const size_t nv = desc.vertex_count, ng = (size_t)desc.group_count;
+    const uint64_t stride = (uint64_t)desc.data_texture_width * (uint64_t)desc.group_data_rows;
+
+    // the reference's arrays (the literal kernel's inputs): copies on the device
+    HIP_TRY(s->positions.copy_of(desc.vertex_positions, nv * 12));
+    HIP_TRY(s->normals32.copy_of(desc.vertex_normals, nv * 12));
+    HIP_TRY(s->boxmin.copy_of(desc.group_boxmin, ng * 12));
+    HIP_TRY(s->boxmax.copy_of(desc.group_boxmax, ng * 12));
+    HIP_TRY(s->objects.copy_of(desc.group_objects, ng * 8));
+    HIP_TRY(s->hitmiss.copy_of(desc.group_hitmiss, (size_t)stride * 8 * 8));
+    HIP_TRY(s->counters.upload(nullptr, sizeof(DeviceCounters) * kCounterShards));
+    if (const int rc = derive_arrays(s.get(), nv, &t, f.index_of, -1))
+        return rc;
+    fill_view(s.get(), desc);
     *out_scene = s.release();
     return SHRAY_OK;
 }

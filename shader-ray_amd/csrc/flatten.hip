@@ -16,16 +16,13 @@
 // bit for bit (tests/test_gpu_flatten.py, against the reference-generated fixtures in tests/golden).
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <vector>
 
 #include "device_tree_internal.h"
+#include "error_internal.h"
 #include "shader_ray_hip.h"
-
-extern "C" int shrayi_fail(int code, const char *message);   // capi.hip: sets shray_last_error()
 
 namespace {
 
@@ -153,16 +150,6 @@ struct shray_device_flat {
     std::vector<float> host[9];
 };
 
-#define FLAT_TRY(expr)                                                                                           \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) {                                                                                  \
-            char msg_[256];                                                                                      \
-            snprintf(msg_, sizeof(msg_), "%s failed: %s", #expr, hipGetErrorString(e_));                         \
-            return shrayi_fail(e_ == hipErrorOutOfMemory ? SHRAY_ERR_OUT_OF_MEMORY : SHRAY_ERR_DEVICE, msg_); \
-        }                                                                                                        \
-    } while (0)
-
 // The flattening proper: the tree and the mesh are on the device already.
 static int flatten_on_device(const TreeView &view, const int *d_tri_vertices, const float *d_vertex_data, int tris, uint32_t width,
                              shray_device_flat **out_flat)
@@ -174,16 +161,16 @@ static int flatten_on_device(const TreeView &view, const int *d_tri_vertices, co
     const int node_rows = (int)(((uint32_t)n + width - 1) / width);
     const size_t vertex_texels = (size_t)width * vertex_rows, node_texels = (size_t)width * node_rows;
 
-    FLAT_TRY(flat->index_of.zeros(sizeof(int) * (size_t)n));
-    FLAT_TRY(flat->positions.zeros(sizeof(float) * 3 * vertex_texels));
-    FLAT_TRY(flat->normals.zeros(sizeof(float) * 3 * vertex_texels));
-    FLAT_TRY(flat->colors.zeros(sizeof(float) * 3 * vertex_texels));
-    FLAT_TRY(flat->boxmin.zeros(sizeof(float) * 3 * node_texels));
-    FLAT_TRY(flat->boxmax.zeros(sizeof(float) * 3 * node_texels));
-    FLAT_TRY(flat->directions.zeros(sizeof(float) * 3 * node_texels));
-    FLAT_TRY(flat->children.zeros(sizeof(float) * 2 * node_texels));
-    FLAT_TRY(flat->objects.zeros(sizeof(float) * 2 * node_texels));
-    FLAT_TRY(flat->hitmiss.zeros(sizeof(float) * 16 * node_texels));
+    HIP_TRY(flat->index_of.zeros(sizeof(int) * (size_t)n));
+    HIP_TRY(flat->positions.zeros(sizeof(float) * 3 * vertex_texels));
+    HIP_TRY(flat->normals.zeros(sizeof(float) * 3 * vertex_texels));
+    HIP_TRY(flat->colors.zeros(sizeof(float) * 3 * vertex_texels));
+    HIP_TRY(flat->boxmin.zeros(sizeof(float) * 3 * node_texels));
+    HIP_TRY(flat->boxmax.zeros(sizeof(float) * 3 * node_texels));
+    HIP_TRY(flat->directions.zeros(sizeof(float) * 3 * node_texels));
+    HIP_TRY(flat->children.zeros(sizeof(float) * 2 * node_texels));
+    HIP_TRY(flat->objects.zeros(sizeof(float) * 2 * node_texels));
+    HIP_TRY(flat->hitmiss.zeros(sizeof(float) * 16 * node_texels));
 
     const int block = 256;
     if (corners)
@@ -196,9 +183,9 @@ static int flatten_on_device(const TreeView &view, const int *d_tri_vertices, co
                        (float *)flat->boxmax.p, (float *)flat->directions.p, (float *)flat->children.p, (float *)flat->objects.p);
     hipLaunchKernelGGL(thread_links, dim3(node_grid.x, 8), dim3(block), 0, nullptr, view, (const int *)d_index,
                        (float *)flat->hitmiss.p, 2 * node_texels);
-    FLAT_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     int root_index = 0;
-    FLAT_TRY(hipMemcpy(&root_index, d_index, sizeof(int), hipMemcpyDeviceToHost));   // also waits for the kernels
+    HIP_TRY(hipMemcpy(&root_index, d_index, sizeof(int), hipMemcpyDeviceToHost));   // also waits for the kernels
 
     shray_scene_desc &d = flat->desc;
     d.struct_size = (uint32_t)sizeof(d);
@@ -254,15 +241,15 @@ int shray_flatten_device(const shray_tree_desc *tree, uint32_t width, shray_devi
             return shrayi_fail(SHRAY_ERR_BAD_TREE, "tree: a triangle names a vertex outside the mesh");
 
     DeviceArray d_parent, d_negative, d_positive, d_start, d_triangles, d_box, d_direction, d_tri_vertices, d_vertex_data;
-    FLAT_TRY(d_parent.upload(tree->node_parent, sizeof(int) * (size_t)n));
-    FLAT_TRY(d_negative.upload(tree->node_negative, sizeof(int) * (size_t)n));
-    FLAT_TRY(d_positive.upload(tree->node_positive, sizeof(int) * (size_t)n));
-    FLAT_TRY(d_start.upload(tree->node_start, sizeof(int) * (size_t)n));
-    FLAT_TRY(d_triangles.upload(tree->node_triangles, sizeof(int) * (size_t)n));
-    FLAT_TRY(d_box.upload(tree->node_box, sizeof(float) * 6 * (size_t)n));
-    FLAT_TRY(d_direction.upload(tree->node_direction, sizeof(float) * 3 * (size_t)n));
-    FLAT_TRY(d_tri_vertices.upload(tree->triangle_vertices, sizeof(int) * 3 * (size_t)tris));
-    FLAT_TRY(d_vertex_data.upload(tree->vertex_data, sizeof(float) * 9 * (size_t)tree->vertex_count));
+    HIP_TRY(d_parent.upload(tree->node_parent, sizeof(int) * (size_t)n));
+    HIP_TRY(d_negative.upload(tree->node_negative, sizeof(int) * (size_t)n));
+    HIP_TRY(d_positive.upload(tree->node_positive, sizeof(int) * (size_t)n));
+    HIP_TRY(d_start.upload(tree->node_start, sizeof(int) * (size_t)n));
+    HIP_TRY(d_triangles.upload(tree->node_triangles, sizeof(int) * (size_t)n));
+    HIP_TRY(d_box.upload(tree->node_box, sizeof(float) * 6 * (size_t)n));
+    HIP_TRY(d_direction.upload(tree->node_direction, sizeof(float) * 3 * (size_t)n));
+    HIP_TRY(d_tri_vertices.upload(tree->triangle_vertices, sizeof(int) * 3 * (size_t)tris));
+    HIP_TRY(d_vertex_data.upload(tree->vertex_data, sizeof(float) * 9 * (size_t)tree->vertex_count));
     const TreeView view{n, (const int *)d_parent.p, (const int *)d_negative.p, (const int *)d_positive.p, (const int *)d_start.p,
                         (const int *)d_triangles.p, (const float *)d_box.p, (const float *)d_direction.p};
     return flatten_on_device(view, (const int *)d_tri_vertices.p, (const float *)d_vertex_data.p, tris, width, out_flat);
@@ -309,7 +296,7 @@ int shray_device_flat_download(shray_device_flat *flat, shray_scene_desc *desc)
     for (int k = 0; k < 9; k++) {
         flat->host[k].resize(arrays[k].floats);
         if (arrays[k].floats)
-            FLAT_TRY(hipMemcpy(flat->host[k].data(), arrays[k].device, sizeof(float) * arrays[k].floats, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(flat->host[k].data(), arrays[k].device, sizeof(float) * arrays[k].floats, hipMemcpyDeviceToHost));
     }
     *desc = d;
     desc->vertex_positions = flat->host[0].data();

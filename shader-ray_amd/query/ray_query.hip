@@ -8,38 +8,17 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 
+#include "error_internal.h"
 #include "kernel_stack_common.h"
 #include "scene_access_internal.h"
 #include "shader_ray_query.h"
 #include "threaded_traversal.h"
 
-extern "C" int shrayi_fail(int code, const char *message);   // capi.hip: sets shray_last_error()
-
 using namespace shray;
 
 namespace {
-
-int fail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return shrayi_fail(code, buf);
-}
-
-#define HIP_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        const hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess)                                                                                          \
-            return fail(e_ == hipErrorOutOfMemory ? SHRAY_ERR_OUT_OF_MEMORY : SHRAY_ERR_DEVICE, "%s failed: %s", #expr, \
-                        hipGetErrorString(e_));                                                                        \
-    } while (0)
 
 constexpr int kThreadedBlock = 256;
 // rays per launch: a larger count is split (the grid's threads must stay below 2^32; and a launch of this size fills the

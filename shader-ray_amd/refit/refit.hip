@@ -14,40 +14,19 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <vector>
 
+#include "error_internal.h"
 #include "half_bits.h"
 #include "packed_layout.h"
 #include "scene_access_internal.h"
 #include "shader_ray_refit.h"
 
-extern "C" int shrayi_fail(int code, const char *message);   // capi.hip: sets shray_last_error()
-
 using namespace shray;
 
 namespace {
-
-int fail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return shrayi_fail(code, buf);
-}
-
-#define HIP_TRY(expr)                                                                                                  \
-    do {                                                                                                               \
-        const hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess)                                                                                          \
-            return fail(e_ == hipErrorOutOfMemory ? SHRAY_ERR_OUT_OF_MEMORY : SHRAY_ERR_DEVICE, "%s failed: %s", #expr, \
-                        hipGetErrorString(e_));                                                                        \
-    } while (0)
 
 constexpr int kBlock = 256;
 constexpr int kTailBlock = 1024;          // heights with at most this many branches run in the one-workgroup launch

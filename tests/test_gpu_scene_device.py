@@ -2,7 +2,8 @@
 shray_scene_create_from_device -- the tree is built, flattened and turned into a scene without leaving the device.  Everything
 the host path derives (shray_scene_create: the packed tree and its eight octant copies, the packed triangles, the pair records, the
 fp16 normals, the deepest ray stack) is read back from both scenes and compared bit for bit; frames and work counters of the two
-scenes are identical; the host's group tree (world.h:48-51) can still be had on demand."""
+scenes are identical; the host's group tree (world.h:48-51) can still be had on demand.  On the golden scenes both scenes' arrays
+also equal the numpy restatement of tests/scene_ref.py bit for bit."""
 import ctypes as C
 import os
 
@@ -10,6 +11,8 @@ import numpy as np
 import pytest
 
 import helpers
+import refit_ref as R
+import scene_ref as S
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -36,6 +39,16 @@ def test_device_pipeline_equals_the_host_path_on_the_golden_scenes(pkg, gpu, nam
     path = os.path.join(GOLDEN, name)
     host_world, host_scene, device = both_scenes(pkg, path)
     assert_same_derived_arrays(host_scene, device.scene, name)
+    # both against the restatement, from the host build's tree and flattened arrays
+    restated = S.derived_arrays(R.TreeArrays.of(host_world.export_tree()), host_world.arrays())
+    restated["packed_tris"] = restated["packed_tris"][:-1]          # (the spare record is not read back)
+    for scene, what in ((host_scene, "host path"), (device.scene, "device path")):
+        got = scene.derived_arrays()
+        assert got["stack_levels"] == restated["stack_levels"], (name, what, got["stack_levels"], restated["stack_levels"])
+        for key in ("packed_nodes", "packed_tris", "normals16", "pair_nodes"):
+            assert got[key].shape == restated[key].shape, (name, what, key, got[key].shape, restated[key].shape)
+            differing = int((got[key] != restated[key]).sum())
+            assert differing == 0, f"{name}, {what}: {differing} words of {key} differ from the restatement's"
     # the reference-layout arrays too (what the literal kernel reads), against the reference's own dump
     flat, ref = device.flat_arrays(), dict(np.load(os.path.splitext(path)[0] + ".ref.npz"))
     for key, value in host_world.arrays().items():
