@@ -14,6 +14,7 @@ HOST_LIB = os.environ.get("SHRAY_HOST_LIB") or os.path.join(PKG_DIR, "libshray_h
 DIST_LIB = os.path.join(PKG_DIR, "libshray_dist.so")
 QUERY_LIB = os.path.join(PKG_DIR, "libshray_query.so")
 REFIT_LIB = os.path.join(PKG_DIR, "libshray_refit.so")
+INSTANCE_LIB = os.path.join(PKG_DIR, "libshray_instance.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
 HIP_LIB = os.environ.get("SHRAY_HIP_LIB") or os.path.join(PKG_DIR, "libshray_hip.so")
 
@@ -282,11 +283,34 @@ REFIT_SYMBOLS = [
     ("shray_scene_geometry_counts", C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 ]
 
+# include/shader_ray_instance.h ---------------------------------------------------------------------------
+INSTANCE_MAX = 1 << 20
+
+
+class Instance(C.Structure):
+    """shray_instance: a resident scene and its row-major 3 x 4 object-to-world map."""
+    _fields_ = [("scene", C.c_void_p), ("object_to_world", C.c_float * 12)]
+
+
+INSTANCE_SYMBOLS = [
+    ("shray_instance_set_create", C.c_int, [C.POINTER(Instance), C.c_int32, C.POINTER(C.c_void_p)]),
+    ("shray_instance_set_update", C.c_int, [C.c_void_p, c_float_p]),
+    ("shray_instance_set_destroy", None, [C.c_void_p]),
+    ("shray_instance_set_count", C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    ("shray_instance_set_world_to_object", C.c_int, [C.c_void_p, c_float_p]),
+    ("shray_trace_instances_device", C.c_int, [C.c_void_p, C.POINTER(QueryParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]),
+    ("shray_trace_instances", C.c_int, [C.c_void_p, C.POINTER(QueryParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("shray_trace_instances_counters", C.c_int, [C.c_void_p, C.POINTER(QueryParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(Counters)]),
+]
+
 _host = None
 _hip = None
 _dist = None
 _query = None
 _refit = None
+_instance = None
 
 
 def _bind(lib, table):
@@ -356,6 +380,18 @@ def load_refit():
             raise RuntimeError(f"{REFIT_LIB} is not built; run `python __graft_entry__.py build` (or `make -C shader-ray_amd`)")
         _refit = _bind(C.CDLL(REFIT_LIB), REFIT_SYMBOLS)
     return _refit
+
+
+def load_instance():
+    """Loads the instanced-query library (libshray_instance.so: a client of libshray_hip.so; its errors are read with
+    shray_last_error)."""
+    global _instance
+    if _instance is None:
+        load_hip()
+        if not os.path.exists(INSTANCE_LIB):
+            raise RuntimeError(f"{INSTANCE_LIB} is not built; run `python __graft_entry__.py build` (or `make -C shader-ray_amd`)")
+        _instance = _bind(C.CDLL(INSTANCE_LIB), INSTANCE_SYMBOLS)
+    return _instance
 
 
 def check_dist(code: int):

@@ -139,15 +139,7 @@ class Scene:
         """Ray queries from host memory (shray_trace_rays, blocking).  `rays`: a RAY_DTYPE array, or [n, 6] / [n, 8] float32
         (origin, direction / the shray_ray layout); `tmax` (scalar or [n]) replaces the rays' own.  Returns a HIT_DTYPE array,
         and with counters=True also the walk's counters (shray_trace_rays_counters)."""
-        rays = np.asarray(rays)
-        if rays.dtype != RAY_DTYPE:
-            a = np.asarray(rays, np.float32)
-            if a.ndim != 2 or a.shape[1] not in (6, 8):
-                raise ValueError("rays must be a RAY_DTYPE array or [n, 6] (origin, direction) / [n, 8] (shray_ray) float32")
-            rays = make_rays(a[:, 0:3], a[:, 3:6]) if a.shape[1] == 6 else np.ascontiguousarray(a).view(RAY_DTYPE).reshape(-1)
-        rays = np.ascontiguousarray(rays).copy() if tmax is not None else np.ascontiguousarray(rays)
-        if tmax is not None:
-            rays["tmax"] = np.asarray(tmax, np.float32)
+        rays = _host_rays(rays, tmax)
         hits = np.empty(len(rays), HIT_DTYPE)
         qp = query_params(any_hit, max_bvh_iterations, max_leaf_tests)
         lib = N.load_query()
@@ -273,6 +265,20 @@ def _host_if_cpu(a):
 # a ray buffer / hit array of the query (include/shader_ray_query.h): 32 and 16 bytes per element
 RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("tmax", np.float32), ("direction", np.float32, 3), ("reserved", np.float32)])
 HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), ("triangle", np.int32)])
+
+
+def _host_rays(rays, tmax=None) -> np.ndarray:
+    """Scene.trace_rays's ray forms as one contiguous RAY_DTYPE array (a copy when `tmax` replaces the rays' own)."""
+    rays = np.asarray(rays)
+    if rays.dtype != RAY_DTYPE:
+        a = np.asarray(rays, np.float32)
+        if a.ndim != 2 or a.shape[1] not in (6, 8):
+            raise ValueError("rays must be a RAY_DTYPE array or [n, 6] (origin, direction) / [n, 8] (shray_ray) float32")
+        rays = make_rays(a[:, 0:3], a[:, 3:6]) if a.shape[1] == 6 else np.ascontiguousarray(a).view(RAY_DTYPE).reshape(-1)
+    rays = np.ascontiguousarray(rays).copy() if tmax is not None else np.ascontiguousarray(rays)
+    if tmax is not None:
+        rays["tmax"] = np.asarray(tmax, np.float32)
+    return rays
 
 
 def make_rays(origins, directions, tmax=None) -> np.ndarray:
@@ -451,6 +457,113 @@ class DeviceWorld:
         if getattr(self, "_world_handle", None):
             self._host.shray_host_free_world(self._world_handle)
             self._world_handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class InstanceSet:
+    """Placed copies of resident scenes, traced together (include/shader_ray_instance.h): `scenes` is a list of Scene or
+    DeviceWorld objects, all on one device (one entry per instance; an object may repeat), `transforms` [n, 3, 4] float32
+    row-major object-to-world maps.  The set keeps references to the objects it was given (a DeviceWorld too: closing it
+    destroys its scene), so they outlive it."""
+
+    def __init__(self, scenes, transforms):
+        self._lib = N.load_instance()
+        self._owners = list(scenes)
+        self._scenes = [s.scene if isinstance(s, DeviceWorld) else s for s in self._owners]
+        n = len(self._scenes)
+        m = self._transforms(transforms, n)
+        array = (N.Instance * max(n, 1))()
+        for i, scene in enumerate(self._scenes):
+            if not isinstance(scene, Scene) or not getattr(scene, "_handle", None):
+                raise TypeError(f"instance {i}: not an open Scene or DeviceWorld")
+            array[i].scene = scene._handle
+            C.memmove(array[i].object_to_world, m[i].ctypes.data, 48)
+        handle = C.c_void_p()
+        N.check(self._lib.shray_instance_set_create(array, n, C.byref(handle)))
+        self._handle = handle
+        self.count = n
+        self.device = self._scenes[0].device_index()
+
+    @staticmethod
+    def _transforms(transforms, n: int) -> np.ndarray:
+        m = np.ascontiguousarray(transforms, dtype=np.float32)
+        if m.shape != (n, 3, 4):
+            raise ValueError(f"transforms must be [{n}, 3, 4] float32, got {list(m.shape)}")
+        return m
+
+    def update(self, transforms=None):
+        """New object-to-world maps ([n, 3, 4]) or None to keep them; re-reads every member scene (call it after refitting one)."""
+        if transforms is None:
+            N.check(self._lib.shray_instance_set_update(self._handle, None))
+            return
+        m = self._transforms(transforms, self.count)
+        N.check(self._lib.shray_instance_set_update(self._handle, m.ctypes.data_as(N.c_float_p)))
+
+    def world_to_object(self) -> np.ndarray:
+        """W of every instance, [n, 3, 4] float32: the float rounding of the inverse map, as the query applies it."""
+        out = np.zeros((self.count, 3, 4), np.float32)
+        N.check(self._lib.shray_instance_set_world_to_object(self._handle, out.ctypes.data_as(N.c_float_p)))
+        return out
+
+    def trace_rays(self, rays, tmax=None, any_hit: bool = False, max_bvh_iterations: int = 400, max_leaf_tests: int = 10,
+                   counters: bool = False):
+        """World-space ray queries (Scene.trace_rays's forms, blocking).  A float32 [n, 8] torch tensor on the set's device takes
+        the device path; one on another device is refused.  Returns (hits: HIT_DTYPE, instances: int32), and with counters=True
+        also the walks' counters."""
+        qp = query_params(any_hit, max_bvh_iterations, max_leaf_tests)
+        rays = _host_if_cpu(rays)
+        if _is_torch(rays):
+            import torch
+            if rays.device.index != self.device:
+                raise ValueError(f"rays are on {rays.device}, the set on cuda:{self.device}")
+            if counters:
+                raise ValueError("counters are counted on the host path: pass host rays")
+            r = rays if tmax is None else rays.clone()
+            if r.dtype != torch.float32 or r.dim() != 2 or r.shape[1] != 8:
+                raise ValueError("a GPU ray tensor must be float32 [n, 8] (the shray_ray layout)")
+            r = r.contiguous()
+            if tmax is not None:
+                r[:, 3] = torch.as_tensor(tmax, dtype=torch.float32, device=r.device)
+            hits = torch.empty((len(r), 4), dtype=torch.int32, device=r.device)
+            inst = torch.empty(len(r), dtype=torch.int32, device=r.device)
+            stream = torch.cuda.current_stream(r.device)
+            N.check(self._lib.shray_trace_instances_device(self._handle, C.byref(qp), C.c_void_p(r.data_ptr()), len(r),
+                                                           C.c_void_p(hits.data_ptr()), C.c_void_p(inst.data_ptr()),
+                                                           C.c_void_p(stream.cuda_stream)))
+            stream.synchronize()
+            return np.ascontiguousarray(hits.cpu().numpy()).view(HIT_DTYPE).reshape(-1), inst.cpu().numpy()
+        rays = _host_rays(rays, tmax)
+        hits = np.empty(len(rays), HIT_DTYPE)
+        inst = np.empty(len(rays), np.int32)
+        args = (self._handle, C.byref(qp), rays.ctypes.data_as(C.c_void_p), len(rays), hits.ctypes.data_as(C.c_void_p),
+                inst.ctypes.data_as(C.c_void_p))
+        if counters:
+            c = N.Counters()
+            N.check(self._lib.shray_trace_instances_counters(*args, C.byref(c)))
+            return hits, inst, c.as_dict()
+        N.check(self._lib.shray_trace_instances(*args))
+        return hits, inst
+
+    def trace_rays_into(self, rays_ptr: int, count: int, hits_ptr: int, instances_ptr: int = 0, stream_ptr: int = 0,
+                        any_hit: bool = False, max_bvh_iterations: int = 400, max_leaf_tests: int = 10):
+        """Asynchronous world-space ray queries on device memory of the set's device (shray_trace_instances_device): `count`
+        shray_ray records at `rays_ptr` -> shray_hit records at `hits_ptr` and, unless `instances_ptr` is 0, int32 instance
+        indices there, on a HIP stream (`stream_ptr`, e.g. torch.cuda.current_stream().cuda_stream)."""
+        qp = query_params(any_hit, max_bvh_iterations, max_leaf_tests)
+        N.check(self._lib.shray_trace_instances_device(self._handle, C.byref(qp), C.c_void_p(rays_ptr), count, C.c_void_p(hits_ptr),
+                                                       C.c_void_p(instances_ptr or None), C.c_void_p(stream_ptr)))
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            self._lib.shray_instance_set_destroy(self._handle)
+            self._handle = None
+        self._scenes = []
+        self._owners = []
 
     def __del__(self):
         try:
