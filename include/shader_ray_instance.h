@@ -43,6 +43,24 @@
  *     (hipDeviceSynchronize) before they read the root boxes, so a refit enqueued before the call, on any stream, is complete
  *     by then; a refit another thread enqueues during the call is not ordered with it.  A failed update leaves the set as
  *     it was.
+ *   - shray_instance_set_update_device is the same update, enqueued on a HIP stream: it builds, on the set's device, the set
+ *     shray_instance_set_update would build from the same transforms and member scenes, bit for bit (top-level nodes, W
+ *     records, scene views), so every later query's hits, instances and counters are the host update's too.  (The one
+ *     exception is the sign of a zero box coordinate in a node over a world box of zero extent at the origin, which the host's
+ *     fold leaves to its order.)  Member root
+ *     boxes are read on the device, ordered after earlier work on its stream (a refit enqueued there before it), and member
+ *     views are re-read on the host without waiting.  It neither waits for the device nor copies anything back to the host.
+ *     A query enqueued later on the same stream sees the new set; work on other streams that reads the set, and updates of
+ *     one set made on different streams, are ordered by the caller, as with a refit.  d_object_to_world is read when the
+ *     update runs, so it stays alive and unchanged until then.
+ *   - A device update validates every transform on the device by the host's rules.  If any is refused, the update writes
+ *     nothing: the set keeps its previous transforms and arrays, as after a failed host update, and
+ *     shray_instance_set_update_status reports the lowest refused instance.  A NULL set, or a d_object_to_world that is not
+ *     4-byte aligned or not device memory of the set's device holding count * 12 floats, fails at the call with
+ *     SHRAY_ERR_INVALID_ARGUMENT and enqueues nothing (update_status still reports the update before it).
+ *   - The set's transforms are those of the last applied update, host or device.  shray_instance_set_update(set, NULL) and
+ *     shray_instance_set_world_to_object wait for a device update and read its result back; a host update after a device
+ *     update is the host update alone.
  *   - The set holds the scene handles, not copies: destroying a member scene while a set uses it is the caller's error.
  *     All member scenes live on one device.
  *
@@ -77,6 +95,15 @@ int shray_instance_set_create(const shray_instance *instances, int32_t count, sh
 
 /* New transforms (count * 12 floats, instance order), or NULL to keep them; re-reads the member scenes either way. */
 int shray_instance_set_update(shray_instance_set *set, const float *object_to_world);
+
+/* Asynchronous, on hip_stream (NULL: the null stream): the set's new object-to-world maps, count * 12 floats (row-major 3 x 4,
+ * instance order) in device memory of the set's device, or NULL to keep the current ones; every member scene's root box is
+ * re-read on the device, ordered after earlier work on hip_stream.  A refused update changes nothing (see update_status). */
+int shray_instance_set_update_device(shray_instance_set *set, const float *d_object_to_world, void *hip_stream);
+
+/* Blocks until the most recent update_device has finished.  *refused = -1 if it was applied (or none was made), otherwise the
+ * lowest instance index whose transform was refused; that update changed nothing. */
+int shray_instance_set_update_status(shray_instance_set *set, int32_t *refused);
 
 void shray_instance_set_destroy(shray_instance_set *set);
 

@@ -298,11 +298,17 @@ INSTANCE_SYMBOLS = [
     ("shray_instance_set_destroy", None, [C.c_void_p]),
     ("shray_instance_set_count", C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     ("shray_instance_set_world_to_object", C.c_int, [C.c_void_p, c_float_p]),
+    ("shray_instance_set_update_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("shray_instance_set_update_status", C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     ("shray_trace_instances_device", C.c_int, [C.c_void_p, C.POINTER(QueryParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                C.c_void_p]),
     ("shray_trace_instances", C.c_int, [C.c_void_p, C.POINTER(QueryParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     ("shray_trace_instances_counters", C.c_int, [C.c_void_p, C.POINTER(QueryParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                  C.POINTER(Counters)]),
+]
+# exported for the tests, not in the header: the set's top-level nodes and records as the next query reads them
+INSTANCE_INTERNAL_SYMBOLS = [
+    ("shrayi_instance_set_arrays", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
 ]
 
 _host = None
@@ -390,7 +396,7 @@ def load_instance():
         load_hip()
         if not os.path.exists(INSTANCE_LIB):
             raise RuntimeError(f"{INSTANCE_LIB} is not built; run `python __graft_entry__.py build` (or `make -C shader-ray_amd`)")
-        _instance = _bind(C.CDLL(INSTANCE_LIB), INSTANCE_SYMBOLS)
+        _instance = _bind(_bind(C.CDLL(INSTANCE_LIB), INSTANCE_SYMBOLS), INSTANCE_INTERNAL_SYMBOLS)
     return _instance
 
 

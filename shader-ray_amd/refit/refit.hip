@@ -18,6 +18,7 @@
 #include <memory>
 #include <vector>
 
+#include "device_array_check.h"
 #include "error_internal.h"
 #include "half_bits.h"
 #include "packed_layout.h"
@@ -497,32 +498,6 @@ int refit_device(shray_scene *scene, const ShrayRefitScene &v, const shray_refit
 
 bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
 
-// A device-path array must be device memory of the scene's device whose allocation holds all `bytes` of it: a host pointer
-// (a CPU tensor, a numpy buffer) or a buffer on another GPU would be read by the validation kernel itself, and a short buffer
-// read past its end.  Refused here, before any launch.
-int check_device_array(const void *p, size_t bytes, int device, const char *what)
-{
-    hipPointerAttribute_t attr;
-    memset(&attr, 0, sizeof(attr));
-    const hipError_t e = hipPointerGetAttributes(&attr, p);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();     // (an unknown pointer is an answer here, not an error for the calls after this one)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "%s is not device memory (hipPointerGetAttributes: %s)", what, hipGetErrorString(e));
-    }
-    if (attr.type != hipMemoryTypeDevice || attr.device != device)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "%s is not device memory of the scene's device %d (memory type %d, device %d)", what,
-                    device, (int)attr.type, attr.device);
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "%s: its allocation is unknown", what);
-    }
-    if ((const char *)p + bytes > (const char *)base + size)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "%s: %zu bytes from it run past the end of its allocation", what, bytes);
-    return SHRAY_OK;
-}
-
 }   // namespace
 
 extern "C" {
@@ -536,9 +511,9 @@ int shray_scene_refit_device(shray_scene *scene, const shray_refit_input *in, sh
     if (!aligned4(in->vertex_data) || !aligned4(in->triangle_vertices))
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "vertex_data and triangle_vertices must be 4-byte aligned");
     const size_t vertex_bytes = (size_t)in->vertex_count * (size_t)in->vertex_stride_floats * sizeof(float);
-    int rc2 = vertex_bytes ? check_device_array(in->vertex_data, vertex_bytes, v.device, "vertex_data") : SHRAY_OK;
+    int rc2 = vertex_bytes ? check_device_array(in->vertex_data, vertex_bytes, v.device, "vertex_data", "scene") : SHRAY_OK;
     if (!rc2 && in->triangle_vertices && v.triangle_count)
-        rc2 = check_device_array(in->triangle_vertices, 3 * (size_t)v.triangle_count * sizeof(int32_t), v.device, "triangle_vertices");
+        rc2 = check_device_array(in->triangle_vertices, 3 * (size_t)v.triangle_count * sizeof(int32_t), v.device, "triangle_vertices", "scene");
     if (rc2)
         return rc2;
     return refit_device(scene, v, in, stats, (hipStream_t)hip_stream);

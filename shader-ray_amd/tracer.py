@@ -497,12 +497,41 @@ class InstanceSet:
         return m
 
     def update(self, transforms=None):
-        """New object-to-world maps ([n, 3, 4]) or None to keep them; re-reads every member scene (call it after refitting one)."""
+        """New object-to-world maps ([n, 3, 4]) or None to keep them; re-reads every member scene (call it after refitting one).
+        A float32 [n, 3, 4] torch tensor on the set's device takes the device path (shray_instance_set_update_device) on torch's
+        current stream and returns without waiting: a refused map raises nothing here, update_status() reports it.  One on
+        another device is refused; numpy arrays and CPU tensors take the blocking host path."""
+        transforms = _host_if_cpu(transforms)
+        if _is_torch(transforms):
+            import torch
+            if transforms.device.index != self.device:
+                raise ValueError(f"transforms are on {transforms.device}, the set on cuda:{self.device}")
+            if transforms.dtype != torch.float32 or tuple(transforms.shape) != (self.count, 3, 4):
+                raise ValueError(f"a GPU transform tensor must be float32 [{self.count}, 3, 4], got {transforms.dtype} "
+                                 f"{list(transforms.shape)}")
+            m = transforms.contiguous()
+            stream = torch.cuda.current_stream(m.device)
+            m.record_stream(stream)   # (the update reads it after this call returns)
+            self.update_into(m.data_ptr(), stream.cuda_stream)
+            return
         if transforms is None:
             N.check(self._lib.shray_instance_set_update(self._handle, None))
             return
         m = self._transforms(transforms, self.count)
         N.check(self._lib.shray_instance_set_update(self._handle, m.ctypes.data_as(N.c_float_p)))
+
+    def update_into(self, transforms_ptr: int, stream_ptr: int = 0):
+        """The asynchronous update on device memory of the set's device (shray_instance_set_update_device): count * 12 float32
+        object-to-world maps at `transforms_ptr`, or 0 to keep the current ones, on a HIP stream (`stream_ptr`, e.g.
+        torch.cuda.current_stream().cuda_stream).  The array must stay alive until the update has run."""
+        N.check(self._lib.shray_instance_set_update_device(self._handle, C.c_void_p(transforms_ptr or None), C.c_void_p(stream_ptr)))
+
+    def update_status(self) -> int:
+        """Waits for the most recent device update: -1 if it was applied (or none was made), else the lowest instance index whose
+        transform was refused (that update changed nothing)."""
+        refused = C.c_int32()
+        N.check(self._lib.shray_instance_set_update_status(self._handle, C.byref(refused)))
+        return refused.value
 
     def world_to_object(self) -> np.ndarray:
         """W of every instance, [n, 3, 4] float32: the float rounding of the inverse map, as the query applies it."""
