@@ -15,6 +15,7 @@ DIST_LIB = os.path.join(PKG_DIR, "libshray_dist.so")
 QUERY_LIB = os.path.join(PKG_DIR, "libshray_query.so")
 REFIT_LIB = os.path.join(PKG_DIR, "libshray_refit.so")
 INSTANCE_LIB = os.path.join(PKG_DIR, "libshray_instance.so")
+POINT_LIB = os.path.join(PKG_DIR, "libshray_point.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
 HIP_LIB = os.environ.get("SHRAY_HIP_LIB") or os.path.join(PKG_DIR, "libshray_hip.so")
 
@@ -311,12 +312,36 @@ INSTANCE_INTERNAL_SYMBOLS = [
     ("shrayi_instance_set_arrays", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
 ]
 
+# include/shader_ray_point.h ------------------------------------------------------------------------------
+REGION_A, REGION_B, REGION_C, REGION_AB, REGION_AC, REGION_BC, REGION_FACE, REGION_NONE = 0, 1, 2, 3, 4, 5, 6, -1
+POINT_MAX_HEIGHT = 128
+
+
+class Point(C.Structure):
+    """shray_point: an object-space point and its squared search radius (16 bytes)."""
+    _fields_ = [("p", C.c_float * 3), ("max_dist2", C.c_float)]
+
+
+class Closest(C.Structure):
+    """shray_closest: the nearest surface point, its squared distance, the weights of corners b and c, the triangle
+    (HIT_MISS or the scene's triangle index) and the region (REGION_*) (32 bytes)."""
+    _fields_ = [("q", C.c_float * 3), ("dist2", C.c_float), ("u", C.c_float), ("v", C.c_float), ("triangle", C.c_int32),
+                ("region", C.c_int32)]
+
+
+POINT_SYMBOLS = [
+    ("shray_closest_points_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("shray_closest_points", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    ("shray_closest_points_counters", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(Counters)]),
+]
+
 _host = None
 _hip = None
 _dist = None
 _query = None
 _refit = None
 _instance = None
+_point = None
 
 
 def _bind(lib, table):
@@ -398,6 +423,18 @@ def load_instance():
             raise RuntimeError(f"{INSTANCE_LIB} is not built; run `python __graft_entry__.py build` (or `make -C shader-ray_amd`)")
         _instance = _bind(_bind(C.CDLL(INSTANCE_LIB), INSTANCE_SYMBOLS), INSTANCE_INTERNAL_SYMBOLS)
     return _instance
+
+
+def load_point():
+    """Loads the closest-point library (libshray_point.so: a client of libshray_hip.so; its errors are read with
+    shray_last_error)."""
+    global _point
+    if _point is None:
+        load_hip()
+        if not os.path.exists(POINT_LIB):
+            raise RuntimeError(f"{POINT_LIB} is not built; run `python __graft_entry__.py build` (or `make -C shader-ray_amd`)")
+        _point = _bind(C.CDLL(POINT_LIB), POINT_SYMBOLS)
+    return _point
 
 
 def check_dist(code: int):

@@ -79,6 +79,7 @@ struct shray_scene {
     DeviceBuffer flat_of_packed;     // int32 per packed node: its number in the flattener's arrays (boxmin, boxmax, objects);
                                      // recorded when packed_ok, for the refit (scene_access_internal.h)
     std::shared_ptr<void> refit_state;   // what libshray_refit.so keeps for this scene (its level order, scratch): freed with it
+    std::shared_ptr<void> point_state;   // what libshray_point.so keeps for this scene (the tree's height): freed with it
     DeviceBuffer env;
     DeviceBuffer counters;
 
@@ -1366,6 +1367,14 @@ int shrayi_scene_refit_view(shray_scene *scene, ShrayRefitScene *out)
     out->packed_ok = scene->packed_ok;
     out->device = scene->device;
     out->state = &scene->refit_state;
+    return SHRAY_OK;
+}
+
+int shrayi_scene_point_state(shray_scene *scene, std::shared_ptr<void> **out)
+{
+    if (!scene || !out)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene is NULL");
+    *out = &scene->point_state;
     return SHRAY_OK;
 }
 

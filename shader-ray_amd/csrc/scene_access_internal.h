@@ -1,5 +1,6 @@
 // scene_access_internal.h -- what libshray_query.so (query/) reads of a scene that capi.hip created: the device views the
-// kernels take, and the FrameView a render would build; and what libshray_refit.so (refit/) rewrites in place.  Host-only,
+// kernels take, and the FrameView a render would build; what libshray_refit.so (refit/) rewrites in place; and the slot where
+// libshray_point.so (point/) keeps what it learns of a scene.  Host-only,
 // internal to the libraries; not part of the C ABI.
 #pragma once
 
@@ -41,3 +42,6 @@ struct ShrayRefitScene {
 extern "C" int shrayi_scene_refit_view(shray_scene *scene, ShrayRefitScene *out);
 // the host-side flag every launch passes by value (SceneView::exact_div_ok): set after a refit from its new boxes
 extern "C" int shrayi_scene_set_exact_div_ok(shray_scene *scene, uint32_t ok);
+
+// libshray_point.so's own per-scene data (include/shader_ray_point.h: the tree's height), destroyed with the scene
+extern "C" int shrayi_scene_point_state(shray_scene *scene, std::shared_ptr<void> **out);

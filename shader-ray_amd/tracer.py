@@ -160,6 +160,54 @@ class Scene:
         N.check(N.load_query().shray_trace_rays_device(self._handle, C.byref(qp), C.c_void_p(rays_ptr), count, C.c_void_p(hits_ptr),
                                                        C.c_void_p(stream_ptr)))
 
+    def closest_points(self, points, max_dist2=None, counters: bool = False):
+        """Closest-point queries (include/shader_ray_point.h): the nearest point of the surface to each point.  `points`: a
+        POINT_DTYPE array or [n, 3] / [n, 4] float32 (p / the shray_point layout), numpy (the blocking host path,
+        shray_closest_points) or a float32 [n, 3] / [n, 4] GPU tensor on the scene's device (shray_closest_points_device, enqueued on the
+        current torch stream); `max_dist2` (scalar or [n]) replaces the points' own (default for [n, 3]: +inf, no limit).  Returns
+        a CLOSEST_DTYPE array for host points, an int32 [n, 8] tensor of shray_closest records (view it as float32 for q, dist2,
+        u, v) for GPU points; with counters=True (host points only) also the walk's counters (shray_closest_points_counters)."""
+        lib = N.load_point()
+        points = _host_if_cpu(points)
+        if _is_torch(points):
+            import torch
+            if counters:
+                raise ValueError("counters are counted on the host path: pass host points")
+            if points.device.index != self.device_index():
+                raise ValueError(f"points are on {points.device}, the scene on cuda:{self.device_index()}")
+            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] not in (3, 4):
+                raise ValueError("a GPU point tensor must be float32 [n, 3] (p) or [n, 4] (the shray_point layout)")
+            if points.shape[1] == 3:
+                pts = torch.empty((len(points), 4), dtype=torch.float32, device=points.device)
+                pts[:, :3] = points
+                pts[:, 3] = float("inf")
+            else:
+                pts = points.contiguous()
+            if max_dist2 is not None:
+                pts = pts.clone() if pts is points else pts
+                pts[:, 3] = torch.as_tensor(max_dist2, dtype=torch.float32, device=pts.device)
+            out = torch.empty((len(pts), 8), dtype=torch.int32, device=pts.device)
+            stream = torch.cuda.current_stream(pts.device)
+            N.check(lib.shray_closest_points_device(self._handle, C.c_void_p(pts.data_ptr()), len(pts), C.c_void_p(out.data_ptr()),
+                                                    C.c_void_p(stream.cuda_stream)))
+            return out
+        pts = _host_points(points, max_dist2)
+        out = np.empty(len(pts), CLOSEST_DTYPE)
+        if counters:
+            c = N.Counters()
+            N.check(lib.shray_closest_points_counters(self._handle, pts.ctypes.data_as(C.c_void_p), len(pts),
+                                                      out.ctypes.data_as(C.c_void_p), C.byref(c)))
+            return out, c.as_dict()
+        N.check(lib.shray_closest_points(self._handle, pts.ctypes.data_as(C.c_void_p), len(pts), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def closest_points_into(self, points_ptr: int, count: int, out_ptr: int, stream_ptr: int = 0):
+        """Asynchronous closest-point queries on device memory of the scene's device (shray_closest_points_device): `count`
+        shray_point records at `points_ptr` (e.g. a float32 [n, 4] tensor's data_ptr()) -> `count` shray_closest records at
+        `out_ptr` (e.g. [n, 8] int32 / float32), on a HIP stream (`stream_ptr`, e.g. torch.cuda.current_stream().cuda_stream)."""
+        N.check(N.load_point().shray_closest_points_device(self._handle, C.c_void_p(points_ptr), count, C.c_void_p(out_ptr),
+                                                           C.c_void_p(stream_ptr)))
+
     def primary_hits(self, params: N.FrameParams, width: int, height: int) -> np.ndarray:
         """The hit of every pixel's 1-spp primary ray (shray_primary_hits_device): HIT_DTYPE [height, width], row 0 = bottom."""
         import torch
@@ -291,6 +339,36 @@ def make_rays(origins, directions, tmax=None) -> np.ndarray:
     return rays
 
 
+# a point buffer / result array of the closest-point query (include/shader_ray_point.h): 16 and 32 bytes per element
+POINT_DTYPE = np.dtype([("p", np.float32, 3), ("max_dist2", np.float32)])
+CLOSEST_DTYPE = np.dtype([("q", np.float32, 3), ("dist2", np.float32), ("u", np.float32), ("v", np.float32), ("triangle", np.int32),
+                          ("region", np.int32)])
+
+
+def _host_points(points, max_dist2=None) -> np.ndarray:
+    """Scene.closest_points's host point forms as one contiguous POINT_DTYPE array (a copy when `max_dist2` replaces the
+    points' own)."""
+    points = np.asarray(points)
+    if points.dtype != POINT_DTYPE:
+        a = np.asarray(points, np.float32)
+        if a.ndim != 2 or a.shape[1] not in (3, 4):
+            raise ValueError("points must be a POINT_DTYPE array or [n, 3] (p) / [n, 4] (shray_point) float32")
+        points = make_points(a) if a.shape[1] == 3 else np.ascontiguousarray(a).view(POINT_DTYPE).reshape(-1)
+    points = np.ascontiguousarray(points).copy() if max_dist2 is not None else np.ascontiguousarray(points)
+    if max_dist2 is not None:
+        points["max_dist2"] = np.asarray(max_dist2, np.float32)
+    return points
+
+
+def make_points(p, max_dist2=None) -> np.ndarray:
+    """A POINT_DTYPE array from [n, 3] points; max_dist2: a scalar or [n] (default +inf: no limit)."""
+    p = np.asarray(p, np.float32).reshape(-1, 3)
+    out = np.zeros(len(p), POINT_DTYPE)
+    out["p"] = p
+    out["max_dist2"] = np.float32(np.inf) if max_dist2 is None else np.asarray(max_dist2, np.float32)
+    return out
+
+
 def query_params(any_hit: bool = False, max_bvh_iterations: int = 400, max_leaf_tests: int = 10) -> N.QueryParams:
     qp = N.QueryParams()
     N.load_query().shray_query_params_init(C.byref(qp))
@@ -407,6 +485,14 @@ class DeviceWorld:
     def trace_rays_into(self, rays_ptr: int, count: int, hits_ptr: int, stream_ptr: int = 0, **kwargs):
         """Scene.trace_rays_into on this scene."""
         return self.scene.trace_rays_into(rays_ptr, count, hits_ptr, stream_ptr, **kwargs)
+
+    def closest_points(self, points, **kwargs):
+        """Scene.closest_points on this scene."""
+        return self.scene.closest_points(points, **kwargs)
+
+    def closest_points_into(self, points_ptr: int, count: int, out_ptr: int, stream_ptr: int = 0):
+        """Scene.closest_points_into on this scene."""
+        return self.scene.closest_points_into(points_ptr, count, out_ptr, stream_ptr)
 
     def primary_hits(self, params: N.FrameParams, width: int, height: int) -> np.ndarray:
         """Scene.primary_hits on this scene."""
