@@ -337,11 +337,7 @@ POINT_SYMBOLS = [
 
 _host = None
 _hip = None
-_dist = None
-_query = None
-_refit = None
-_instance = None
-_point = None
+_clients = {}   # path -> the loaded client library of libshray_hip.so
 
 
 def _bind(lib, table):
@@ -380,61 +376,41 @@ def load_hip():
     return _hip
 
 
-def load_dist():
-    """Loads the multi-GPU frame loop (libshray_dist.so: depends on libshray_hip.so and RCCL)."""
-    global _dist
-    if _dist is None:
-        load_hip()    # torch first, then the HIP layer: one HIP runtime, one RCCL (torch bundles both)
-        if not os.path.exists(DIST_LIB):
-            raise RuntimeError(f"{DIST_LIB} is not built; run `python __graft_entry__.py build` (or `make -C shader-ray_amd`)")
-        _dist = _bind(C.CDLL(DIST_LIB), DIST_SYMBOLS)
-    return _dist
-
-
-def load_query():
-    """Loads the ray-query library (libshray_query.so: a client of libshray_hip.so; its errors are read with shray_last_error)."""
-    global _query
-    if _query is None:
+def _load_client(path, symbols):
+    """Loads a library that is a client of libshray_hip.so: the HIP layer first (torch, then it: one HIP runtime), then the
+    library."""
+    if path not in _clients:
         load_hip()
-        if not os.path.exists(QUERY_LIB):
-            raise RuntimeError(f"{QUERY_LIB} is not built; run `python __graft_entry__.py build` (or `make -C shader-ray_amd`)")
-        _query = _bind(C.CDLL(QUERY_LIB), QUERY_SYMBOLS)
-    return _query
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} is not built; run `python __graft_entry__.py build` (or `make -C shader-ray_amd`)")
+        _clients[path] = _bind(C.CDLL(path), symbols)
+    return _clients[path]
+
+
+def load_dist():
+    """Loads the multi-GPU frame loop (libshray_dist.so: depends on libshray_hip.so and RCCL; torch bundles both)."""
+    return _load_client(DIST_LIB, DIST_SYMBOLS)
+
+
+# the client libraries below report their errors through shray_last_error
+def load_query():
+    """Loads the ray-query library (libshray_query.so)."""
+    return _load_client(QUERY_LIB, QUERY_SYMBOLS)
 
 
 def load_refit():
-    """Loads the refit library (libshray_refit.so: a client of libshray_hip.so; its errors are read with shray_last_error)."""
-    global _refit
-    if _refit is None:
-        load_hip()
-        if not os.path.exists(REFIT_LIB):
-            raise RuntimeError(f"{REFIT_LIB} is not built; run `python __graft_entry__.py build` (or `make -C shader-ray_amd`)")
-        _refit = _bind(C.CDLL(REFIT_LIB), REFIT_SYMBOLS)
-    return _refit
+    """Loads the refit library (libshray_refit.so)."""
+    return _load_client(REFIT_LIB, REFIT_SYMBOLS)
 
 
 def load_instance():
-    """Loads the instanced-query library (libshray_instance.so: a client of libshray_hip.so; its errors are read with
-    shray_last_error)."""
-    global _instance
-    if _instance is None:
-        load_hip()
-        if not os.path.exists(INSTANCE_LIB):
-            raise RuntimeError(f"{INSTANCE_LIB} is not built; run `python __graft_entry__.py build` (or `make -C shader-ray_amd`)")
-        _instance = _bind(_bind(C.CDLL(INSTANCE_LIB), INSTANCE_SYMBOLS), INSTANCE_INTERNAL_SYMBOLS)
-    return _instance
+    """Loads the instanced-query library (libshray_instance.so), with its test accessor."""
+    return _load_client(INSTANCE_LIB, INSTANCE_SYMBOLS + INSTANCE_INTERNAL_SYMBOLS)
 
 
 def load_point():
-    """Loads the closest-point library (libshray_point.so: a client of libshray_hip.so; its errors are read with
-    shray_last_error)."""
-    global _point
-    if _point is None:
-        load_hip()
-        if not os.path.exists(POINT_LIB):
-            raise RuntimeError(f"{POINT_LIB} is not built; run `python __graft_entry__.py build` (or `make -C shader-ray_amd`)")
-        _point = _bind(C.CDLL(POINT_LIB), POINT_SYMBOLS)
-    return _point
+    """Loads the closest-point library (libshray_point.so)."""
+    return _load_client(POINT_LIB, POINT_SYMBOLS)
 
 
 def check_dist(code: int):

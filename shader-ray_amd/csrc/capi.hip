@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "counters_internal.h"
 #include "device_types.h"
 #include "error_internal.h"
 #include "frame_params_defaults.h"
@@ -1633,28 +1634,14 @@ int shray_render_counters(shray_scene *scene, const shray_frame_params *params, 
     if (rc)
         return rc;
     HIP_TRY(hipDeviceSynchronize());
-    DeviceCounters shards[kCounterShards];
-    HIP_TRY(hipMemcpy(shards, scene->counters.p, sizeof(shards), hipMemcpyDeviceToHost));
-    DeviceCounters dc = {};
-    for (const DeviceCounters &sh : shards) {
-        dc.node_visits += sh.node_visits;
-        dc.leaf_visits += sh.leaf_visits;
-        dc.triangle_tests += sh.triangle_tests;
-        dc.shaded_hits += sh.shaded_hits;
-        dc.env_lookups += sh.env_lookups;
-        dc.traversals += sh.traversals;
-        dc.bad_hits += sh.bad_hits;
-    }
+    shray_counters sum = {};
+    rc = sum_counter_shards((const DeviceCounters *)scene->counters.p, &sum);
+    if (rc)
+        return rc;
     if (rgba_out_host)
         HIP_TRY(hipMemcpy(rgba_out_host, frame.p, bytes, hipMemcpyDeviceToHost));
-    counters->node_visits = dc.node_visits;
-    counters->leaf_visits = dc.leaf_visits;
-    counters->triangle_tests = dc.triangle_tests;
-    counters->shaded_hits = dc.shaded_hits;
-    counters->env_lookups = dc.env_lookups;
-    counters->traversals = dc.traversals;
-    counters->bad_hits = dc.bad_hits;
-    counters->samples = (uint64_t)width * height * spp;
+    sum.samples = (uint64_t)width * height * spp;
+    *counters = sum;   // (the caller's counters are written only on success)
     return SHRAY_OK;
 }
 
@@ -1688,18 +1675,9 @@ int shray_render_counters_timed(shray_scene *scene, const shray_frame_params *pa
     if (rc)
         return rc;
     HIP_TRY(hipDeviceSynchronize());
-    DeviceCounters shards[kCounterShards];
-    HIP_TRY(hipMemcpy(shards, scene->counters.p, sizeof(shards), hipMemcpyDeviceToHost));
-    memset(counters, 0, sizeof(*counters));
-    for (const DeviceCounters &sh : shards) {
-        counters->node_visits += sh.node_visits;
-        counters->leaf_visits += sh.leaf_visits;
-        counters->triangle_tests += sh.triangle_tests;
-        counters->shaded_hits += sh.shaded_hits;
-        counters->env_lookups += sh.env_lookups;
-        counters->traversals += sh.traversals;
-        counters->bad_hits += sh.bad_hits;
-    }
+    rc = sum_counter_shards((const DeviceCounters *)scene->counters.p, counters);
+    if (rc)
+        return rc;
     counters->samples = (uint64_t)width * height * spp;
     if (rgba_out_host)
         HIP_TRY(hipMemcpy(rgba_out_host, frame.p, bytes, hipMemcpyDeviceToHost));

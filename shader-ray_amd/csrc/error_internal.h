@@ -1,6 +1,6 @@
-// error_internal.h -- how libshray_hip.so, libshray_query.so and libshray_refit.so report an error: the message goes to
-// shray_last_error() (capi.hip keeps it, per thread) and the code is returned.  Host-only, internal to the libraries; not part
-// of the C ABI.
+// error_internal.h -- how libshray_hip.so and its client libraries (libshray_query.so, libshray_refit.so, libshray_instance.so,
+// libshray_point.so) report an error: the message goes to shray_last_error() (capi.hip keeps it, per thread) and the code is
+// returned.  Host-only, internal to the libraries; not part of the C ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -20,6 +20,7 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/functional.hpp>
 
+#include "client_internal.h"
 #include "device_array_check.h"
 #include "error_internal.h"
 #include "kernel_stack_common.h"
@@ -179,8 +180,6 @@ __global__ void __launch_bounds__(kBatchBlock, COUNT ? SHRAY_MIN_WAVES_VIEW : SH
         add_counters(rc, w.counters);
     }
 }
-
-bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1u)) == 0; }
 
 // max and min as std::max / std::min take them: the first argument on a tie
 __host__ __device__ inline double dmax(double a, double b) { return (a < b) ? b : a; }
@@ -621,20 +620,6 @@ __global__ void __launch_bounds__(kUpdateBlock) iu_commit(uint32_t n, const TopN
         views[k] = new_views[k];
 }
 
-struct DeviceBuffer {
-    void *p = nullptr;
-    DeviceBuffer() = default;
-    DeviceBuffer(const DeviceBuffer &) = delete;
-    DeviceBuffer &operator=(const DeviceBuffer &) = delete;
-    ~DeviceBuffer()
-    {
-        if (p)
-            (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    template <typename T> T *as() const { return static_cast<T *>(p); }
-};
-
 // pinned host memory a copy reads from, free again once `copied` has completed
 struct Staging {
     void *host = nullptr;
@@ -693,23 +678,9 @@ int make_set(const std::vector<shray_scene *> &scenes, const float *object_to_wo
     return upload(p, d);
 }
 
-int set_device_of(const shray_instance_set *set)
-{
-    int current = -1;
-    if (hipGetDevice(&current) != hipSuccess || current != set->host.device)
-        HIP_TRY(hipSetDevice(set->host.device));
-    return SHRAY_OK;
-}
-
 // ---- the device update's host side -------------------------------------------------------------------------------------------
 
 unsigned int blocks_of(size_t items) { return (unsigned int)((items + kUpdateBlock - 1) / kUpdateBlock); }
-
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SHRAY_OK : fail(SHRAY_ERR_DEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
-}
 
 // the scratch of the device update, made once per set on its device; the ids are written on `stream`
 int make_update(shray_instance_set *set, hipStream_t stream, std::unique_ptr<DeviceUpdate> &out)
@@ -791,7 +762,7 @@ int refresh_host(shray_instance_set *set)
 {
     if (!set->host_stale)
         return SHRAY_OK;
-    int rc = set_device_of(set);
+    int rc = use_device(set->host.device);
     if (rc)
         return rc;
     const size_t n = set->scenes.size();
@@ -819,7 +790,7 @@ int update_device(shray_instance_set *set, const float *d_object_to_world, hipSt
 {
     if (!set)
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "set is NULL");
-    int rc = set_device_of(set);
+    int rc = use_device(set->host.device);
     if (rc)
         return rc;
     const uint32_t n = (uint32_t)set->scenes.size();
@@ -922,7 +893,7 @@ int trace_device(shray_instance_set *set, const shray_query_params *qp, const sh
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "ray and hit buffers must be 16-byte aligned, the instance buffer 4-byte aligned");
     if (count == 0)
         return SHRAY_OK;
-    rc = set_device_of(set);
+    rc = use_device(set->host.device);
     if (rc)
         return rc;
     const FrameView fr = query_frame(qp);
@@ -932,9 +903,8 @@ int trace_device(shray_instance_set *set, const shray_query_params *qp, const sh
     const uint64_t blocks = ((uint64_t)count + kBatchBlock - 1) / kBatchBlock, per_launch = kRaysPerLaunch / kBatchBlock;
     QueryWork w{(const float4 *)d_rays, (float4 *)d_hits, (uint64_t)count, 0, d_counters};
     const SetDevice &d = set->dev;
-    for (uint64_t first = 0; first < blocks; first += per_launch) {
+    return for_each_launch(blocks, per_launch, [&](uint64_t first, dim3 grid) {
         w.first_block = first;
-        const dim3 grid((unsigned int)(blocks - first < per_launch ? blocks - first : per_launch));
         if (d_counters)
             hipLaunchKernelGGL((instance_kernel<true, false>), grid, dim3(kBatchBlock), lds, stream, w, d.nodes, d.records, d.views,
                                d_instances, fr, levels, top_offset);
@@ -944,11 +914,8 @@ int trace_device(shray_instance_set *set, const shray_query_params *qp, const sh
         else
             hipLaunchKernelGGL((instance_kernel<false, false>), grid, dim3(kBatchBlock), lds, stream, w, d.nodes, d.records, d.views,
                                d_instances, fr, levels, top_offset);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return fail(SHRAY_ERR_DEVICE, "instance query launch failed: %s", hipGetErrorString(e));
-    }
-    return SHRAY_OK;
+        return launched("instance query");
+    });
 }
 
 // the blocking forms: the rays to the device, the query on the null stream, the results (and tallies) back
@@ -968,50 +935,15 @@ int trace_host(shray_instance_set *set, const shray_query_params *qp, const shra
     }
     if (count == 0)
         return SHRAY_OK;
-    rc = set_device_of(set);
+    rc = use_device(set->host.device);
     if (rc)
         return rc;
-    struct Buffers {
-        void *rays = nullptr, *hits = nullptr, *instances = nullptr, *counters = nullptr;
-        ~Buffers()
-        {
-            for (void *p : {rays, hits, instances, counters})
-                if (p)
-                    (void)hipFree(p);
-        }
-    } b;
-    const size_t ray_bytes = (size_t)count * sizeof(shray_ray), hit_bytes = (size_t)count * sizeof(shray_hit);
-    const size_t instance_bytes = (size_t)count * sizeof(int32_t);
-    HIP_TRY(hipMalloc(&b.rays, ray_bytes));
-    HIP_TRY(hipMalloc(&b.hits, hit_bytes));
-    if (instances)
-        HIP_TRY(hipMalloc(&b.instances, instance_bytes));
-    if (out) {
-        HIP_TRY(hipMalloc(&b.counters, sizeof(DeviceCounters) * kCounterShards));
-        HIP_TRY(hipMemset(b.counters, 0, sizeof(DeviceCounters) * kCounterShards));
-    }
-    HIP_TRY(hipMemcpy(b.rays, rays, ray_bytes, hipMemcpyHostToDevice));
-    rc = trace_device(set, qp, (const shray_ray *)b.rays, count, (shray_hit *)b.hits, (int32_t *)b.instances, nullptr,
-                      (DeviceCounters *)b.counters);
-    if (rc)
-        return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    if (hits)
-        HIP_TRY(hipMemcpy(hits, b.hits, hit_bytes, hipMemcpyDeviceToHost));
-    if (instances)
-        HIP_TRY(hipMemcpy(instances, b.instances, instance_bytes, hipMemcpyDeviceToHost));
-    if (out) {
-        DeviceCounters shards[kCounterShards];
-        HIP_TRY(hipMemcpy(shards, b.counters, sizeof(shards), hipMemcpyDeviceToHost));
-        for (const DeviceCounters &s : shards) {
-            out->node_visits += s.node_visits;
-            out->leaf_visits += s.leaf_visits;
-            out->triangle_tests += s.triangle_tests;
-            out->traversals += s.traversals;
-            out->bad_hits += s.bad_hits;
-        }
-    }
-    return SHRAY_OK;
+    const size_t n = (size_t)count;
+    return run_blocking({{rays, n * sizeof(shray_ray)}}, {{hits, n * sizeof(shray_hit)}, {instances, instances ? n * sizeof(int32_t) : 0}}, out,
+                        [&](DeviceBuffer *d_rays, DeviceBuffer *d_out, DeviceCounters *shards) {
+                            return trace_device(set, qp, d_rays->as<const shray_ray>(), count, d_out[0].as<shray_hit>(),
+                                                d_out[1].as<int32_t>(), nullptr, shards);
+                        });
 }
 
 }   // namespace
@@ -1084,7 +1016,7 @@ int shray_instance_set_update_status(shray_instance_set *set, int32_t *refused)
     *refused = -1;
     if (!set->update || !set->update->enqueued)
         return SHRAY_OK;
-    const int rc = set_device_of(set);
+    const int rc = use_device(set->host.device);
     if (rc)
         return rc;
     HIP_TRY(hipEventSynchronize(set->update->finished));
@@ -1132,7 +1064,7 @@ int shrayi_instance_set_arrays(const shray_instance_set *set, void *nodes, void 
         *node_count = (int32_t)(2 * n - 1);
     if (!nodes && !records)
         return SHRAY_OK;
-    const int rc = set_device_of(set);
+    const int rc = use_device(set->host.device);
     if (rc)
         return rc;
     if (set->update && set->update->enqueued)

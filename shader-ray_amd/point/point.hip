@@ -11,6 +11,7 @@
 #include <memory>
 #include <vector>
 
+#include "client_internal.h"
 #include "device_types.h"
 #include "error_internal.h"
 #include "packed_layout.h"
@@ -259,8 +260,6 @@ __global__ void __launch_bounds__(kBlock) closest_point_kernel(SceneView sc, Poi
     }
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-
 // What this library keeps per scene (ShrayRefitScene::state's twin, scene_access_internal.h): the tree's height.
 struct PointState {
     int height;
@@ -314,16 +313,11 @@ int tree_height(const ShrayQueryScene &q, shray_scene *scene, int *height)
 // the scene's query view on its device, with the walk's stack height; refused without a packed tree or when too deep
 int prepare(shray_scene *scene, ShrayQueryScene *q, int *height)
 {
-    if (!scene)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene is NULL");
-    int rc = shrayi_scene_query_view(scene, q);
+    int rc = enter_scene(scene, q);
     if (rc)
         return rc;
     if (!q->packed_ok)
         return fail(SHRAY_ERR_BAD_TREE, "the scene has no packed tree (closest-point queries walk the packed tree)");
-    int current = -1;
-    if (hipGetDevice(&current) != hipSuccess || current != q->device)
-        HIP_TRY(hipSetDevice(q->device));   // the scene's buffers live on its device
     rc = tree_height(*q, scene, height);
     if (rc)
         return rc;
@@ -340,7 +334,7 @@ int closest_device(shray_scene *scene, const shray_point *d_points, int64_t coun
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "negative point count %lld", (long long)count);
     if (!scene || !d_points || !d_out)
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene, points or out is NULL");
-    if (!aligned16(d_points) || !aligned16(d_out))
+    if (!aligned(d_points, 16) || !aligned(d_out, 16))
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "point and record buffers must be 16-byte aligned");
     if (count == 0)
         return SHRAY_OK;
@@ -351,19 +345,15 @@ int closest_device(shray_scene *scene, const shray_point *d_points, int64_t coun
         return rc;
     PointWork w{(const float4 *)d_points, (float4 *)d_out, (uint64_t)count, 0, d_counters};
     const size_t lds = stack_bytes(height);
-    for (uint64_t first = 0; first < (uint64_t)count; first += kPointsPerLaunch) {
-        w.first = first;
-        const uint64_t n = (uint64_t)count - first < kPointsPerLaunch ? (uint64_t)count - first : kPointsPerLaunch;
-        const dim3 grid((unsigned int)((n + kBlock - 1) / kBlock));
+    const uint64_t blocks = ((uint64_t)count + kBlock - 1) / kBlock;
+    return for_each_launch(blocks, kPointsPerLaunch / kBlock, [&](uint64_t first, dim3 grid) {
+        w.first = first * kBlock;
         if (d_counters)
             hipLaunchKernelGGL(closest_point_kernel<true>, grid, dim3(kBlock), lds, stream, q.view, w);
         else
             hipLaunchKernelGGL(closest_point_kernel<false>, grid, dim3(kBlock), lds, stream, q.view, w);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return fail(SHRAY_ERR_DEVICE, "closest-point launch failed: %s", hipGetErrorString(e));
-    }
-    return SHRAY_OK;
+        return launched("closest-point");
+    });
 }
 
 // the blocking forms: the points to the device, the query on the null stream, the records (and tallies) back
@@ -381,42 +371,14 @@ int closest_host(shray_scene *scene, const shray_point *points, int64_t count, s
         return SHRAY_OK;
     ShrayQueryScene q;
     int height = 0;
-    int rc = prepare(scene, &q, &height);   // (the errors of a scene come before any allocation)
+    const int rc = prepare(scene, &q, &height);   // (the errors of a scene come before any allocation)
     if (rc)
         return rc;
-    struct Buffers {
-        void *points = nullptr, *out = nullptr, *counters = nullptr;
-        ~Buffers()
-        {
-            for (void *p : {points, out, counters})
-                if (p)
-                    (void)hipFree(p);
-        }
-    } b;
-    const size_t point_bytes = (size_t)count * sizeof(shray_point), out_bytes = (size_t)count * sizeof(shray_closest);
-    HIP_TRY(hipMalloc(&b.points, point_bytes));
-    HIP_TRY(hipMalloc(&b.out, out_bytes));
-    if (counters) {
-        HIP_TRY(hipMalloc(&b.counters, sizeof(DeviceCounters) * kCounterShards));
-        HIP_TRY(hipMemset(b.counters, 0, sizeof(DeviceCounters) * kCounterShards));
-    }
-    HIP_TRY(hipMemcpy(b.points, points, point_bytes, hipMemcpyHostToDevice));
-    rc = closest_device(scene, (const shray_point *)b.points, count, (shray_closest *)b.out, nullptr, (DeviceCounters *)b.counters);
-    if (rc)
-        return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    if (out)
-        HIP_TRY(hipMemcpy(out, b.out, out_bytes, hipMemcpyDeviceToHost));
-    if (counters) {
-        DeviceCounters shards[kCounterShards];
-        HIP_TRY(hipMemcpy(shards, b.counters, sizeof(shards), hipMemcpyDeviceToHost));
-        for (const DeviceCounters &s : shards) {
-            counters->node_visits += s.node_visits;
-            counters->leaf_visits += s.leaf_visits;
-            counters->triangle_tests += s.triangle_tests;
-        }
-    }
-    return SHRAY_OK;
+    const size_t n = (size_t)count;
+    return run_blocking({{points, n * sizeof(shray_point)}}, {{out, n * sizeof(shray_closest)}}, counters,
+                        [&](DeviceBuffer *d_points, DeviceBuffer *d_out, DeviceCounters *shards) {
+                            return closest_device(scene, d_points->as<const shray_point>(), count, d_out->as<shray_closest>(), nullptr, shards);
+                        });
 }
 
 }   // namespace

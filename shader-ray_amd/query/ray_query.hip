@@ -10,6 +10,7 @@
 #include <climits>
 #include <cstring>
 
+#include "client_internal.h"
 #include "error_internal.h"
 #include "kernel_stack_common.h"
 #include "query_common.h"
@@ -74,21 +75,6 @@ __global__ void __launch_bounds__(kThreadedBlock) query_threaded_kernel(SceneVie
     }
 }
 
-int scene_of(shray_scene *scene, ShrayQueryScene *q)
-{
-    if (!scene)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene is NULL");
-    const int rc = shrayi_scene_query_view(scene, q);
-    if (rc)
-        return rc;
-    int current = -1;
-    if (hipGetDevice(&current) != hipSuccess || current != q->device)
-        HIP_TRY(hipSetDevice(q->device));   // the scene's buffers live on its device
-    return SHRAY_OK;
-}
-
-bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
-
 // `blocks` workgroups of work `w` (first_block = 0), in launches of at most kRaysPerLaunch threads
 int launch_query(const ShrayQueryScene &q, const FrameView &fr, QueryWork w, uint64_t blocks, bool any_hit, hipStream_t stream)
 {
@@ -97,9 +83,8 @@ int launch_query(const ShrayQueryScene &q, const FrameView &fr, QueryWork w, uin
     const uint64_t per_launch = kRaysPerLaunch / (uint64_t)block;
     const size_t lds = stack ? stack_lds_bytes(q.stack_levels, kBatchBlock) : 0;
     const bool count = w.counters != nullptr;
-    for (uint64_t first = 0; first < blocks; first += per_launch) {
+    return for_each_launch(blocks, per_launch, [&](uint64_t first, dim3 grid) {
         w.first_block = first;
-        const dim3 grid((unsigned int)(blocks - first < per_launch ? blocks - first : per_launch));
         if (stack && count)
             hipLaunchKernelGGL((query_stack_kernel<true, false>), grid, dim3(block), lds, stream, q.view, fr, w, q.stack_levels);
         else if (stack && any_hit)
@@ -110,11 +95,8 @@ int launch_query(const ShrayQueryScene &q, const FrameView &fr, QueryWork w, uin
             hipLaunchKernelGGL((query_threaded_kernel<true>), grid, dim3(block), 0, stream, q.view, fr, w);
         else
             hipLaunchKernelGGL((query_threaded_kernel<false>), grid, dim3(block), 0, stream, q.view, fr, w);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return fail(SHRAY_ERR_DEVICE, "ray query launch failed: %s", hipGetErrorString(e));
-    }
-    return SHRAY_OK;
+        return launched("ray query");
+    });
 }
 
 int trace_device(shray_scene *scene, const shray_query_params *qp, const shray_ray *d_rays, int64_t count, shray_hit *d_hits,
@@ -127,12 +109,12 @@ int trace_device(shray_scene *scene, const shray_query_params *qp, const shray_r
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "negative ray count %lld", (long long)count);
     if (!scene || !d_rays || !d_hits)
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene, rays or hits is NULL");
-    if (!aligned16(d_rays) || !aligned16(d_hits))
+    if (!aligned(d_rays, 16) || !aligned(d_hits, 16))
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "ray and hit buffers must be 16-byte aligned");
     if (count == 0)
         return SHRAY_OK;
     ShrayQueryScene q;
-    rc = scene_of(scene, &q);
+    rc = enter_scene(scene, &q);
     if (rc)
         return rc;
     const bool stack = q.packed_ok && q.kernel_id != 1;
@@ -159,44 +141,14 @@ int trace_host(shray_scene *scene, const shray_query_params *qp, const shray_ray
     if (count == 0)
         return SHRAY_OK;
     ShrayQueryScene q;
-    rc = scene_of(scene, &q);
+    rc = enter_scene(scene, &q);
     if (rc)
         return rc;
-    struct Buffers {
-        void *rays = nullptr, *hits = nullptr, *counters = nullptr;
-        ~Buffers()
-        {
-            for (void *p : {rays, hits, counters})
-                if (p)
-                    (void)hipFree(p);
-        }
-    } b;
-    const size_t ray_bytes = (size_t)count * sizeof(shray_ray), hit_bytes = (size_t)count * sizeof(shray_hit);
-    HIP_TRY(hipMalloc(&b.rays, ray_bytes));
-    HIP_TRY(hipMalloc(&b.hits, hit_bytes));
-    if (out) {
-        HIP_TRY(hipMalloc(&b.counters, sizeof(DeviceCounters) * kCounterShards));
-        HIP_TRY(hipMemset(b.counters, 0, sizeof(DeviceCounters) * kCounterShards));
-    }
-    HIP_TRY(hipMemcpy(b.rays, rays, ray_bytes, hipMemcpyHostToDevice));
-    rc = trace_device(scene, qp, (const shray_ray *)b.rays, count, (shray_hit *)b.hits, nullptr, (DeviceCounters *)b.counters);
-    if (rc)
-        return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    if (hits)
-        HIP_TRY(hipMemcpy(hits, b.hits, hit_bytes, hipMemcpyDeviceToHost));
-    if (out) {
-        DeviceCounters shards[kCounterShards];
-        HIP_TRY(hipMemcpy(shards, b.counters, sizeof(shards), hipMemcpyDeviceToHost));
-        for (const DeviceCounters &s : shards) {
-            out->node_visits += s.node_visits;
-            out->leaf_visits += s.leaf_visits;
-            out->triangle_tests += s.triangle_tests;
-            out->traversals += s.traversals;
-            out->bad_hits += s.bad_hits;
-        }
-    }
-    return SHRAY_OK;
+    const size_t n = (size_t)count;
+    return run_blocking({{rays, n * sizeof(shray_ray)}}, {{hits, n * sizeof(shray_hit)}}, out,
+                        [&](DeviceBuffer *d_rays, DeviceBuffer *d_hits, DeviceCounters *shards) {
+                            return trace_device(scene, qp, d_rays->as<const shray_ray>(), count, d_hits->as<shray_hit>(), nullptr, shards);
+                        });
 }
 
 }   // namespace
@@ -239,14 +191,14 @@ int shray_primary_hits_device(shray_scene *scene, const shray_frame_params *para
 {
     if (!scene || !params || !d_hits)
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene, params or hits is NULL");
-    if (!aligned16(d_hits))
+    if (!aligned(d_hits, 16))
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "the hit buffer must be 16-byte aligned");
     FrameView fr;
     int rc = shrayi_frame_view(params, width, height, &fr);
     if (rc)
         return rc;
     ShrayQueryScene q;
-    rc = scene_of(scene, &q);
+    rc = enter_scene(scene, &q);
     if (rc)
         return rc;
     const uint64_t tile = (q.packed_ok && q.kernel_id != 1) ? 8u : 16u;

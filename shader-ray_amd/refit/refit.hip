@@ -18,6 +18,7 @@
 #include <memory>
 #include <vector>
 
+#include "client_internal.h"
 #include "device_array_check.h"
 #include "error_internal.h"
 #include "half_bits.h"
@@ -261,36 +262,13 @@ __global__ void __launch_bounds__(kBlock) rf_finish(uint32_t blocks, const doubl
     }
 }
 
-struct DeviceMemory {
-    void *p = nullptr;
-    size_t bytes = 0;
-    ~DeviceMemory()
-    {
-        if (p)
-            (void)hipFree(p);
-    }
-    hipError_t grow(size_t want)
-    {
-        if (want <= bytes)
-            return hipSuccess;
-        if (p)
-            (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        const hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess)
-            bytes = want;
-        return e;
-    }
-};
-
 // What the refit keeps per scene (the scene owns it: ShrayRefitScene::state): the nodes ordered by height, their topology
 // and the scratch of the passes.  Built by the first refit from the packed tree's child words, which a refit never changes.
 struct RefitState {
     uint32_t n = 0, nt = 0, leaves = 0;
     std::vector<uint32_t> height_start;   // order[height_start[h] .. height_start[h + 1]) have height h; h = 0: the leaves
     uint32_t tail_height = 0;             // first height of the one-workgroup launch
-    DeviceMemory order, topo, heights, boxes, partial, facts, staging;
+    DeviceBuffer order, topo, heights, boxes, partial, facts, staging;
 };
 
 int build_state(const ShrayRefitScene &v, hipStream_t stream, RefitState &st)
@@ -403,16 +381,7 @@ int scene_of(shray_scene *scene, const shray_refit_input *in, ShrayRefitScene *v
                     3u * v->triangle_count);
     if (!v->packed_ok)
         return fail(SHRAY_ERR_BAD_TREE, "the scene has no packed tree (its tables were not proved one canonical tree): it cannot be refit");
-    int current = -1;
-    if (hipGetDevice(&current) != hipSuccess || current != v->device)
-        HIP_TRY(hipSetDevice(v->device));   // the scene's buffers live on its device
-    return SHRAY_OK;
-}
-
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SHRAY_OK : fail(SHRAY_ERR_DEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
+    return use_device(v->device);
 }
 
 unsigned int grid_of(uint64_t items, int block) { return (unsigned int)((items + block - 1) / block); }
@@ -496,8 +465,6 @@ int refit_device(shray_scene *scene, const ShrayRefitScene &v, const shray_refit
     return SHRAY_OK;
 }
 
-bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
-
 }   // namespace
 
 extern "C" {
@@ -508,7 +475,7 @@ int shray_scene_refit_device(shray_scene *scene, const shray_refit_input *in, sh
     const int rc = scene_of(scene, in, &v);
     if (rc)
         return rc;
-    if (!aligned4(in->vertex_data) || !aligned4(in->triangle_vertices))
+    if (!aligned(in->vertex_data, 4) || !aligned(in->triangle_vertices, 4))
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "vertex_data and triangle_vertices must be 4-byte aligned");
     const size_t vertex_bytes = (size_t)in->vertex_count * (size_t)in->vertex_stride_floats * sizeof(float);
     int rc2 = vertex_bytes ? check_device_array(in->vertex_data, vertex_bytes, v.device, "vertex_data", "scene") : SHRAY_OK;
@@ -566,12 +533,12 @@ int shray_scene_geometry_counts(const shray_scene *scene, int32_t *corners, int3
 int shray_scene_geometry_download(const shray_scene *scene, float *positions, float *normals, float *boxmin, float *boxmax)
 {
     ShrayRefitScene v;
-    const int rc = shrayi_scene_refit_view(const_cast<shray_scene *>(scene), &v);
+    int rc = shrayi_scene_refit_view(const_cast<shray_scene *>(scene), &v);
     if (rc)
         return rc;
-    int current = -1;
-    if (hipGetDevice(&current) != hipSuccess || current != v.device)
-        HIP_TRY(hipSetDevice(v.device));
+    rc = use_device(v.device);
+    if (rc)
+        return rc;
     const size_t corner_bytes = 9 * (size_t)v.triangle_count * sizeof(float), node_bytes = 3 * (size_t)v.node_count * sizeof(float);
     if (positions && corner_bytes)
         HIP_TRY(hipMemcpy(positions, v.positions, corner_bytes, hipMemcpyDeviceToHost));

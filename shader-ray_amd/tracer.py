@@ -315,18 +315,25 @@ RAY_DTYPE = np.dtype([("origin", np.float32, 3), ("tmax", np.float32), ("directi
 HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), ("triangle", np.int32)])
 
 
+def _host_records(records, dtype, short, long, build, field, value, form) -> np.ndarray:
+    """`dtype` records, or [n, short] (through `build`) / [n, long] (the C layout) float32, as one contiguous `dtype` array;
+    `value`, unless None, replaces `field` in a copy.  `form` describes the accepted forms in the error."""
+    records = np.asarray(records)
+    if records.dtype != dtype:
+        a = np.asarray(records, np.float32)
+        if a.ndim != 2 or a.shape[1] not in (short, long):
+            raise ValueError(form)
+        records = build(a) if a.shape[1] == short else np.ascontiguousarray(a).view(dtype).reshape(-1)
+    records = np.ascontiguousarray(records).copy() if value is not None else np.ascontiguousarray(records)
+    if value is not None:
+        records[field] = np.asarray(value, np.float32)
+    return records
+
+
 def _host_rays(rays, tmax=None) -> np.ndarray:
     """Scene.trace_rays's ray forms as one contiguous RAY_DTYPE array (a copy when `tmax` replaces the rays' own)."""
-    rays = np.asarray(rays)
-    if rays.dtype != RAY_DTYPE:
-        a = np.asarray(rays, np.float32)
-        if a.ndim != 2 or a.shape[1] not in (6, 8):
-            raise ValueError("rays must be a RAY_DTYPE array or [n, 6] (origin, direction) / [n, 8] (shray_ray) float32")
-        rays = make_rays(a[:, 0:3], a[:, 3:6]) if a.shape[1] == 6 else np.ascontiguousarray(a).view(RAY_DTYPE).reshape(-1)
-    rays = np.ascontiguousarray(rays).copy() if tmax is not None else np.ascontiguousarray(rays)
-    if tmax is not None:
-        rays["tmax"] = np.asarray(tmax, np.float32)
-    return rays
+    return _host_records(rays, RAY_DTYPE, 6, 8, lambda a: make_rays(a[:, 0:3], a[:, 3:6]), "tmax", tmax,
+                         "rays must be a RAY_DTYPE array or [n, 6] (origin, direction) / [n, 8] (shray_ray) float32")
 
 
 def make_rays(origins, directions, tmax=None) -> np.ndarray:
@@ -348,16 +355,8 @@ CLOSEST_DTYPE = np.dtype([("q", np.float32, 3), ("dist2", np.float32), ("u", np.
 def _host_points(points, max_dist2=None) -> np.ndarray:
     """Scene.closest_points's host point forms as one contiguous POINT_DTYPE array (a copy when `max_dist2` replaces the
     points' own)."""
-    points = np.asarray(points)
-    if points.dtype != POINT_DTYPE:
-        a = np.asarray(points, np.float32)
-        if a.ndim != 2 or a.shape[1] not in (3, 4):
-            raise ValueError("points must be a POINT_DTYPE array or [n, 3] (p) / [n, 4] (shray_point) float32")
-        points = make_points(a) if a.shape[1] == 3 else np.ascontiguousarray(a).view(POINT_DTYPE).reshape(-1)
-    points = np.ascontiguousarray(points).copy() if max_dist2 is not None else np.ascontiguousarray(points)
-    if max_dist2 is not None:
-        points["max_dist2"] = np.asarray(max_dist2, np.float32)
-    return points
+    return _host_records(points, POINT_DTYPE, 3, 4, make_points, "max_dist2", max_dist2,
+                         "points must be a POINT_DTYPE array or [n, 3] (p) / [n, 4] (shray_point) float32")
 
 
 def make_points(p, max_dist2=None) -> np.ndarray:
