@@ -16,6 +16,7 @@ QUERY_LIB = os.path.join(PKG_DIR, "libshray_query.so")
 REFIT_LIB = os.path.join(PKG_DIR, "libshray_refit.so")
 INSTANCE_LIB = os.path.join(PKG_DIR, "libshray_instance.so")
 POINT_LIB = os.path.join(PKG_DIR, "libshray_point.so")
+SDF_LIB = os.path.join(PKG_DIR, "libshray_sdf.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
 HIP_LIB = os.environ.get("SHRAY_HIP_LIB") or os.path.join(PKG_DIR, "libshray_hip.so")
 
@@ -335,6 +336,26 @@ POINT_SYMBOLS = [
     ("shray_closest_points_counters", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(Counters)]),
 ]
 
+# include/shader_ray_sdf.h --------------------------------------------------------------------------------
+SIGN_DATA_FLOATS = 21
+
+
+class SurfaceInfo(C.Structure):
+    """shray_surface_info: the welded topology of a scene (56 bytes)."""
+    _fields_ = [("vertices", C.c_int64), ("edges", C.c_int64), ("boundary_edges", C.c_int64), ("nonmanifold_edges", C.c_int64),
+                ("misoriented_edges", C.c_int64), ("degenerate_triangles", C.c_int64), ("closed", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+SDF_SYMBOLS = [
+    ("shray_signed_distance_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("shray_signed_distance", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("shray_scene_surface_info", C.c_int, [C.c_void_p, C.POINTER(SurfaceInfo)]),
+    ("shray_scene_sign_data_download", C.c_int, [C.c_void_p, C.c_void_p]),
+]
+
 _host = None
 _hip = None
 _clients = {}   # path -> the loaded client library of libshray_hip.so
@@ -411,6 +432,11 @@ def load_instance():
 def load_point():
     """Loads the closest-point library (libshray_point.so)."""
     return _load_client(POINT_LIB, POINT_SYMBOLS)
+
+
+def load_sdf():
+    """Loads the signed-distance library (libshray_sdf.so)."""
+    return _load_client(SDF_LIB, SDF_SYMBOLS)
 
 
 def check_dist(code: int):

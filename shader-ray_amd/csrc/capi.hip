@@ -81,6 +81,8 @@ struct shray_scene {
                                      // recorded when packed_ok, for the refit (scene_access_internal.h)
     std::shared_ptr<void> refit_state;   // what libshray_refit.so keeps for this scene (its level order, scratch): freed with it
     std::shared_ptr<void> point_state;   // what libshray_point.so keeps for this scene (the tree's height): freed with it
+    std::shared_ptr<void> sdf_state;     // what libshray_sdf.so keeps for this scene (the sign data, its generation): freed with it
+    uint64_t geometry_generation = 0;    // bumped by every refit that writes new positions (scene_access_internal.h)
     DeviceBuffer env;
     DeviceBuffer counters;
 
@@ -1376,6 +1378,23 @@ int shrayi_scene_point_state(shray_scene *scene, std::shared_ptr<void> **out)
     if (!scene || !out)
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene is NULL");
     *out = &scene->point_state;
+    return SHRAY_OK;
+}
+
+int shrayi_scene_sdf_state(shray_scene *scene, std::shared_ptr<void> **out, uint64_t *generation)
+{
+    if (!scene || !out || !generation)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene is NULL");
+    *out = &scene->sdf_state;
+    *generation = scene->geometry_generation;
+    return SHRAY_OK;
+}
+
+int shrayi_scene_geometry_changed(shray_scene *scene)
+{
+    if (!scene)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene is NULL");
+    scene->geometry_generation++;
     return SHRAY_OK;
 }
 

@@ -1,6 +1,6 @@
 // scene_access_internal.h -- what libshray_query.so (query/) reads of a scene that capi.hip created: the device views the
-// kernels take, and the FrameView a render would build; what libshray_refit.so (refit/) rewrites in place; and the slot where
-// libshray_point.so (point/) keeps what it learns of a scene.  Host-only,
+// kernels take, and the FrameView a render would build; what libshray_refit.so (refit/) rewrites in place; and the slots where
+// libshray_point.so (point/) and libshray_sdf.so (sdf/) keep what they learn of a scene.  Host-only,
 // internal to the libraries; not part of the C ABI.
 #pragma once
 
@@ -45,3 +45,9 @@ extern "C" int shrayi_scene_set_exact_div_ok(shray_scene *scene, uint32_t ok);
 
 // libshray_point.so's own per-scene data (include/shader_ray_point.h: the tree's height), destroyed with the scene
 extern "C" int shrayi_scene_point_state(shray_scene *scene, std::shared_ptr<void> **out);
+
+// libshray_sdf.so's own per-scene data (include/shader_ray_sdf.h: the sign data), destroyed with the scene, and the scene's
+// geometry generation: a host-side count of the refits that wrote new positions.  Host-only, no device work.
+extern "C" int shrayi_scene_sdf_state(shray_scene *scene, std::shared_ptr<void> **out, uint64_t *generation);
+// called by a refit (host or device form) once its validation has passed, before it enqueues the writes of new positions
+extern "C" int shrayi_scene_geometry_changed(shray_scene *scene);

@@ -418,6 +418,8 @@ int refit_device(shray_scene *scene, const ShrayRefitScene &v, const shray_refit
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "a triangle_vertices entry is outside [0, %d)", in->vertex_count);
     if (facts.non_finite)
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "a vertex position or normal is not finite");
+    if (const int rc = shrayi_scene_geometry_changed(scene))   // what a later signed-distance query derived is stale now
+        return rc;
 
     // 2. corners, normals, packed triangles
     if (nt)

@@ -173,19 +173,7 @@ class Scene:
             import torch
             if counters:
                 raise ValueError("counters are counted on the host path: pass host points")
-            if points.device.index != self.device_index():
-                raise ValueError(f"points are on {points.device}, the scene on cuda:{self.device_index()}")
-            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] not in (3, 4):
-                raise ValueError("a GPU point tensor must be float32 [n, 3] (p) or [n, 4] (the shray_point layout)")
-            if points.shape[1] == 3:
-                pts = torch.empty((len(points), 4), dtype=torch.float32, device=points.device)
-                pts[:, :3] = points
-                pts[:, 3] = float("inf")
-            else:
-                pts = points.contiguous()
-            if max_dist2 is not None:
-                pts = pts.clone() if pts is points else pts
-                pts[:, 3] = torch.as_tensor(max_dist2, dtype=torch.float32, device=pts.device)
+            pts = self._device_points(points, max_dist2)
             out = torch.empty((len(pts), 8), dtype=torch.int32, device=pts.device)
             stream = torch.cuda.current_stream(pts.device)
             N.check(lib.shray_closest_points_device(self._handle, C.c_void_p(pts.data_ptr()), len(pts), C.c_void_p(out.data_ptr()),
@@ -207,6 +195,72 @@ class Scene:
         `out_ptr` (e.g. [n, 8] int32 / float32), on a HIP stream (`stream_ptr`, e.g. torch.cuda.current_stream().cuda_stream)."""
         N.check(N.load_point().shray_closest_points_device(self._handle, C.c_void_p(points_ptr), count, C.c_void_p(out_ptr),
                                                            C.c_void_p(stream_ptr)))
+
+    def _device_points(self, points, max_dist2=None):
+        """a float32 [n, 3] / [n, 4] GPU tensor on the scene's device as a contiguous [n, 4] shray_point tensor (a copy when
+        `max_dist2` replaces the points' own)"""
+        import torch
+        if points.device.index != self.device_index():
+            raise ValueError(f"points are on {points.device}, the scene on cuda:{self.device_index()}")
+        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] not in (3, 4):
+            raise ValueError("a GPU point tensor must be float32 [n, 3] (p) or [n, 4] (the shray_point layout)")
+        if points.shape[1] == 3:
+            pts = torch.empty((len(points), 4), dtype=torch.float32, device=points.device)
+            pts[:, :3] = points
+            pts[:, 3] = float("inf")
+        else:
+            pts = points.contiguous()
+        if max_dist2 is not None:
+            pts = pts.clone() if pts is points else pts
+            pts[:, 3] = torch.as_tensor(max_dist2, dtype=torch.float32, device=pts.device)
+        return pts
+
+    def signed_distance(self, points, max_dist2=None, closest: bool = False):
+        """Signed distances to the surface (include/shader_ray_sdf.h): negative inside a closed, outward-wound mesh, NaN for a
+        point with no triangle within its radius.  `points` and `max_dist2` as for closest_points: numpy (the blocking host path,
+        shray_signed_distance) or a GPU tensor on the scene's device (shray_signed_distance_device, enqueued on the current torch
+        stream).  Returns float32 [n] of the same kind; with closest=True also the closest-point records (a CLOSEST_DTYPE array,
+        or an int32 [n, 8] tensor)."""
+        lib = N.load_sdf()
+        points = _host_if_cpu(points)
+        if _is_torch(points):
+            import torch
+            pts = self._device_points(points, max_dist2)
+            out = torch.empty(len(pts), dtype=torch.float32, device=pts.device)
+            rec = torch.empty((len(pts), 8), dtype=torch.int32, device=pts.device) if closest else None
+            stream = torch.cuda.current_stream(pts.device)
+            N.check(lib.shray_signed_distance_device(self._handle, C.c_void_p(pts.data_ptr()), len(pts), C.c_void_p(out.data_ptr()),
+                                                     C.c_void_p(rec.data_ptr() if closest else None), C.c_void_p(stream.cuda_stream)))
+            return (out, rec) if closest else out
+        pts = _host_points(points, max_dist2)
+        out = np.empty(len(pts), np.float32)
+        rec = np.empty(len(pts), CLOSEST_DTYPE) if closest else None
+        N.check(lib.shray_signed_distance(self._handle, pts.ctypes.data_as(C.c_void_p), len(pts), out.ctypes.data_as(C.c_void_p),
+                                          rec.ctypes.data_as(C.c_void_p) if closest else None))
+        return (out, rec) if closest else out
+
+    def signed_distance_into(self, points_ptr: int, count: int, out_ptr: int, closest_ptr: int = 0, stream_ptr: int = 0):
+        """Asynchronous signed distance queries on device memory of the scene's device (shray_signed_distance_device): `count`
+        shray_point records at `points_ptr` -> `count` float32 at `out_ptr` and, unless `closest_ptr` is 0, `count`
+        shray_closest records there, on a HIP stream (`stream_ptr`, e.g. torch.cuda.current_stream().cuda_stream)."""
+        N.check(N.load_sdf().shray_signed_distance_device(self._handle, C.c_void_p(points_ptr), count, C.c_void_p(out_ptr),
+                                                          C.c_void_p(closest_ptr or None), C.c_void_p(stream_ptr)))
+
+    def surface_info(self) -> dict:
+        """The welded topology (shray_scene_surface_info): vertices, edges, boundary_edges, nonmanifold_edges,
+        misoriented_edges, degenerate_triangles, closed."""
+        info = N.SurfaceInfo()
+        N.check(N.load_sdf().shray_scene_surface_info(self._handle, C.byref(info)))
+        return info.as_dict()
+
+    def sign_data(self) -> np.ndarray:
+        """The derived sign data (shray_scene_sign_data_download): float32 [triangles, 7, 3]: nhat, the pseudonormals of the
+        vertices of corners a, b, c, and of the edges AB, AC, BC."""
+        corners = C.c_int32()
+        N.check(N.load_refit().shray_scene_geometry_counts(self._handle, C.byref(corners), None))
+        out = np.zeros((corners.value // 3, 7, 3), np.float32)
+        N.check(N.load_sdf().shray_scene_sign_data_download(self._handle, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def primary_hits(self, params: N.FrameParams, width: int, height: int) -> np.ndarray:
         """The hit of every pixel's 1-spp primary ray (shray_primary_hits_device): HIT_DTYPE [height, width], row 0 = bottom."""
@@ -492,6 +546,22 @@ class DeviceWorld:
     def closest_points_into(self, points_ptr: int, count: int, out_ptr: int, stream_ptr: int = 0):
         """Scene.closest_points_into on this scene."""
         return self.scene.closest_points_into(points_ptr, count, out_ptr, stream_ptr)
+
+    def signed_distance(self, points, **kwargs):
+        """Scene.signed_distance on this scene."""
+        return self.scene.signed_distance(points, **kwargs)
+
+    def signed_distance_into(self, points_ptr: int, count: int, out_ptr: int, closest_ptr: int = 0, stream_ptr: int = 0):
+        """Scene.signed_distance_into on this scene."""
+        return self.scene.signed_distance_into(points_ptr, count, out_ptr, closest_ptr, stream_ptr)
+
+    def surface_info(self) -> dict:
+        """Scene.surface_info on this scene."""
+        return self.scene.surface_info()
+
+    def sign_data(self) -> np.ndarray:
+        """Scene.sign_data on this scene."""
+        return self.scene.sign_data()
 
     def primary_hits(self, params: N.FrameParams, width: int, height: int) -> np.ndarray:
         """Scene.primary_hits on this scene."""
