@@ -17,6 +17,7 @@ REFIT_LIB = os.path.join(PKG_DIR, "libshray_refit.so")
 INSTANCE_LIB = os.path.join(PKG_DIR, "libshray_instance.so")
 POINT_LIB = os.path.join(PKG_DIR, "libshray_point.so")
 SDF_LIB = os.path.join(PKG_DIR, "libshray_sdf.so")
+WINDING_LIB = os.path.join(PKG_DIR, "libshray_winding.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
 HIP_LIB = os.environ.get("SHRAY_HIP_LIB") or os.path.join(PKG_DIR, "libshray_hip.so")
 
@@ -356,6 +357,18 @@ SDF_SYMBOLS = [
     ("shray_scene_sign_data_download", C.c_int, [C.c_void_p, C.c_void_p]),
 ]
 
+# include/shader_ray_winding.h -----------------------------------------------------------------------------
+WINDING_DATA_FLOATS = 20
+
+WINDING_SYMBOLS = [
+    ("shray_winding_number_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
+    ("shray_winding_number", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
+    ("shray_winding_signed_distance_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]),
+    ("shray_winding_signed_distance", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
+    ("shray_scene_winding_data_download", C.c_int, [C.c_void_p, C.c_void_p]),
+]
+
 _host = None
 _hip = None
 _clients = {}   # path -> the loaded client library of libshray_hip.so
@@ -437,6 +450,11 @@ def load_point():
 def load_sdf():
     """Loads the signed-distance library (libshray_sdf.so)."""
     return _load_client(SDF_LIB, SDF_SYMBOLS)
+
+
+def load_winding():
+    """Loads the winding-number library (libshray_winding.so)."""
+    return _load_client(WINDING_LIB, WINDING_SYMBOLS)
 
 
 def check_dist(code: int):

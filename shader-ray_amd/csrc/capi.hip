@@ -82,6 +82,7 @@ struct shray_scene {
     std::shared_ptr<void> refit_state;   // what libshray_refit.so keeps for this scene (its level order, scratch): freed with it
     std::shared_ptr<void> point_state;   // what libshray_point.so keeps for this scene (the tree's height): freed with it
     std::shared_ptr<void> sdf_state;     // what libshray_sdf.so keeps for this scene (the sign data, its generation): freed with it
+    std::shared_ptr<void> winding_state; // what libshray_winding.so keeps for this scene (the node records, their generation): freed with it
     uint64_t geometry_generation = 0;    // bumped by every refit that writes new positions (scene_access_internal.h)
     DeviceBuffer env;
     DeviceBuffer counters;
@@ -1386,6 +1387,15 @@ int shrayi_scene_sdf_state(shray_scene *scene, std::shared_ptr<void> **out, uint
     if (!scene || !out || !generation)
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene is NULL");
     *out = &scene->sdf_state;
+    *generation = scene->geometry_generation;
+    return SHRAY_OK;
+}
+
+int shrayi_scene_winding_state(shray_scene *scene, std::shared_ptr<void> **out, uint64_t *generation)
+{
+    if (!scene || !out || !generation)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene is NULL");
+    *out = &scene->winding_state;
     *generation = scene->geometry_generation;
     return SHRAY_OK;
 }

@@ -1,6 +1,6 @@
 // scene_access_internal.h -- what libshray_query.so (query/) reads of a scene that capi.hip created: the device views the
 // kernels take, and the FrameView a render would build; what libshray_refit.so (refit/) rewrites in place; and the slots where
-// libshray_point.so (point/) and libshray_sdf.so (sdf/) keep what they learn of a scene.  Host-only,
+// libshray_point.so (point/), libshray_sdf.so (sdf/) and libshray_winding.so (winding/) keep what they learn of a scene.  Host-only,
 // internal to the libraries; not part of the C ABI.
 #pragma once
 
@@ -49,5 +49,8 @@ extern "C" int shrayi_scene_point_state(shray_scene *scene, std::shared_ptr<void
 // libshray_sdf.so's own per-scene data (include/shader_ray_sdf.h: the sign data), destroyed with the scene, and the scene's
 // geometry generation: a host-side count of the refits that wrote new positions.  Host-only, no device work.
 extern "C" int shrayi_scene_sdf_state(shray_scene *scene, std::shared_ptr<void> **out, uint64_t *generation);
+// libshray_winding.so's own per-scene data (include/shader_ray_winding.h: the node records), destroyed with the scene, and the
+// same geometry generation.  Host-only, no device work.
+extern "C" int shrayi_scene_winding_state(shray_scene *scene, std::shared_ptr<void> **out, uint64_t *generation);
 // called by a refit (host or device form) once its validation has passed, before it enqueues the writes of new positions
 extern "C" int shrayi_scene_geometry_changed(shray_scene *scene);

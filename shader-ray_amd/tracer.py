@@ -262,6 +262,72 @@ class Scene:
         N.check(N.load_sdf().shray_scene_sign_data_download(self._handle, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def winding_number(self, points, beta: float = 2.0):
+        """Generalized winding numbers (include/shader_ray_winding.h): about 1 inside a closed outward-wound mesh and 0 outside,
+        robust on open and self-intersecting meshes; NaN for a point with a non-finite coordinate.  `points` as for
+        closest_points (a point's max_dist2 is ignored): numpy (the blocking host path, shray_winding_number) or a GPU tensor on
+        the scene's device (shray_winding_number_device, on the current torch stream).  `beta`: the far-field accuracy
+        parameter, float('inf') for the exact sum over every triangle.  Returns float32 [n] of the same kind."""
+        lib = N.load_winding()
+        points = _host_if_cpu(points)
+        if _is_torch(points):
+            import torch
+            pts = self._device_points(points)
+            out = torch.empty(len(pts), dtype=torch.float32, device=pts.device)
+            stream = torch.cuda.current_stream(pts.device)
+            N.check(lib.shray_winding_number_device(self._handle, C.c_void_p(pts.data_ptr()), len(pts), beta, C.c_void_p(out.data_ptr()),
+                                                    C.c_void_p(stream.cuda_stream)))
+            return out
+        pts = _host_points(points)
+        out = np.empty(len(pts), np.float32)
+        N.check(lib.shray_winding_number(self._handle, pts.ctypes.data_as(C.c_void_p), len(pts), beta, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def winding_number_into(self, points_ptr: int, count: int, out_ptr: int, beta: float = 2.0, stream_ptr: int = 0):
+        """Asynchronous winding numbers on device memory of the scene's device (shray_winding_number_device): `count`
+        shray_point records at `points_ptr` -> `count` float32 at `out_ptr`, on a HIP stream (`stream_ptr`)."""
+        N.check(N.load_winding().shray_winding_number_device(self._handle, C.c_void_p(points_ptr), count, beta, C.c_void_p(out_ptr),
+                                                             C.c_void_p(stream_ptr)))
+
+    def winding_signed_distance(self, points, max_dist2=None, beta: float = 2.0, closest: bool = False):
+        """Signed distances whose sign comes from the winding number (shray_winding_signed_distance): negative where w > 0.5,
+        NaN for a point with no triangle within its radius.  Arguments and results as for signed_distance."""
+        lib = N.load_winding()
+        points = _host_if_cpu(points)
+        if _is_torch(points):
+            import torch
+            pts = self._device_points(points, max_dist2)
+            out = torch.empty(len(pts), dtype=torch.float32, device=pts.device)
+            rec = torch.empty((len(pts), 8), dtype=torch.int32, device=pts.device) if closest else None
+            stream = torch.cuda.current_stream(pts.device)
+            N.check(lib.shray_winding_signed_distance_device(self._handle, C.c_void_p(pts.data_ptr()), len(pts), beta,
+                                                             C.c_void_p(out.data_ptr()), C.c_void_p(rec.data_ptr() if closest else None),
+                                                             C.c_void_p(stream.cuda_stream)))
+            return (out, rec) if closest else out
+        pts = _host_points(points, max_dist2)
+        out = np.empty(len(pts), np.float32)
+        rec = np.empty(len(pts), CLOSEST_DTYPE) if closest else None
+        N.check(lib.shray_winding_signed_distance(self._handle, pts.ctypes.data_as(C.c_void_p), len(pts), beta,
+                                                  out.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p) if closest else None))
+        return (out, rec) if closest else out
+
+    def winding_signed_distance_into(self, points_ptr: int, count: int, out_ptr: int, closest_ptr: int = 0, beta: float = 2.0,
+                                     stream_ptr: int = 0):
+        """Asynchronous winding-signed distances on device memory (shray_winding_signed_distance_device), as
+        signed_distance_into."""
+        N.check(N.load_winding().shray_winding_signed_distance_device(self._handle, C.c_void_p(points_ptr), count, beta,
+                                                                      C.c_void_p(out_ptr), C.c_void_p(closest_ptr or None),
+                                                                      C.c_void_p(stream_ptr)))
+
+    def winding_data(self) -> np.ndarray:
+        """The derived node records (shray_scene_winding_data_download): float32 [nodes, 20] in packed pre-order: P, r, N, A,
+        M row-major, three zeros."""
+        nodes = C.c_int32()
+        N.check(N.load_refit().shray_scene_geometry_counts(self._handle, None, C.byref(nodes)))
+        out = np.zeros((nodes.value, N.WINDING_DATA_FLOATS), np.float32)
+        N.check(N.load_winding().shray_scene_winding_data_download(self._handle, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def primary_hits(self, params: N.FrameParams, width: int, height: int) -> np.ndarray:
         """The hit of every pixel's 1-spp primary ray (shray_primary_hits_device): HIT_DTYPE [height, width], row 0 = bottom."""
         import torch
@@ -562,6 +628,27 @@ class DeviceWorld:
     def sign_data(self) -> np.ndarray:
         """Scene.sign_data on this scene."""
         return self.scene.sign_data()
+
+    def winding_number(self, points, **kwargs):
+        """Scene.winding_number on this scene."""
+        return self.scene.winding_number(points, **kwargs)
+
+    def winding_number_into(self, points_ptr: int, count: int, out_ptr: int, beta: float = 2.0, stream_ptr: int = 0):
+        """Scene.winding_number_into on this scene."""
+        return self.scene.winding_number_into(points_ptr, count, out_ptr, beta, stream_ptr)
+
+    def winding_signed_distance(self, points, **kwargs):
+        """Scene.winding_signed_distance on this scene."""
+        return self.scene.winding_signed_distance(points, **kwargs)
+
+    def winding_signed_distance_into(self, points_ptr: int, count: int, out_ptr: int, closest_ptr: int = 0, beta: float = 2.0,
+                                     stream_ptr: int = 0):
+        """Scene.winding_signed_distance_into on this scene."""
+        return self.scene.winding_signed_distance_into(points_ptr, count, out_ptr, closest_ptr, beta, stream_ptr)
+
+    def winding_data(self) -> np.ndarray:
+        """Scene.winding_data on this scene."""
+        return self.scene.winding_data()
 
     def primary_hits(self, params: N.FrameParams, width: int, height: int) -> np.ndarray:
         """Scene.primary_hits on this scene."""
