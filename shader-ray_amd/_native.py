@@ -18,6 +18,7 @@ INSTANCE_LIB = os.path.join(PKG_DIR, "libshray_instance.so")
 POINT_LIB = os.path.join(PKG_DIR, "libshray_point.so")
 SDF_LIB = os.path.join(PKG_DIR, "libshray_sdf.so")
 WINDING_LIB = os.path.join(PKG_DIR, "libshray_winding.so")
+MULTIHIT_LIB = os.path.join(PKG_DIR, "libshray_multihit.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
 HIP_LIB = os.environ.get("SHRAY_HIP_LIB") or os.path.join(PKG_DIR, "libshray_hip.so")
 
@@ -369,6 +370,23 @@ WINDING_SYMBOLS = [
     ("shray_scene_winding_data_download", C.c_int, [C.c_void_p, C.c_void_p]),
 ]
 
+# include/shader_ray_multihit.h ----------------------------------------------------------------------------
+MULTIHIT_MAX = 64
+
+
+class MultihitParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_hits", C.c_int32), ("max_leaf_tests", C.c_int32), ("reserved", C.c_int32)]
+
+
+MULTIHIT_SYMBOLS = [
+    ("shray_multihit_params_init", None, [C.POINTER(MultihitParams)]),
+    ("shray_trace_all_hits_device", C.c_int, [C.c_void_p, C.POINTER(MultihitParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    ("shray_trace_all_hits", C.c_int, [C.c_void_p, C.POINTER(MultihitParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("shray_trace_all_hits_counters", C.c_int, [C.c_void_p, C.POINTER(MultihitParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                C.POINTER(Counters)]),
+]
+
 _host = None
 _hip = None
 _clients = {}   # path -> the loaded client library of libshray_hip.so
@@ -455,6 +473,11 @@ def load_sdf():
 def load_winding():
     """Loads the winding-number library (libshray_winding.so)."""
     return _load_client(WINDING_LIB, WINDING_SYMBOLS)
+
+
+def load_multihit():
+    """Loads the all-hits ray-query library (libshray_multihit.so)."""
+    return _load_client(MULTIHIT_LIB, MULTIHIT_SYMBOLS)
 
 
 def check_dist(code: int):

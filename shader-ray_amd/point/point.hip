@@ -20,46 +20,6 @@ using namespace shray;
 
 namespace {
 
-// What this library keeps per scene (ShrayRefitScene::state's twin, scene_access_internal.h): the tree's height.
-struct PointState {
-    int height;
-};
-
-// The packed tree's height, read once per scene -- the one synchronisation of the device path, on the scene's first query.
-int tree_height(const ShrayQueryScene &q, shray_scene *scene, int *height)
-{
-    std::shared_ptr<void> *slot = nullptr;
-    int rc = shrayi_scene_point_state(scene, &slot);
-    if (rc)
-        return rc;
-    if (*slot) {
-        *height = static_cast<PointState *>(slot->get())->height;
-        return SHRAY_OK;
-    }
-    int deepest = 0;
-    rc = packed_tree_height(q, &deepest);
-    if (rc)
-        return rc;
-    auto st = std::make_shared<PointState>();
-    st->height = deepest;
-    *slot = st;
-    *height = deepest;
-    return SHRAY_OK;
-}
-
-// the scene's query view on its device, with the walk's stack height; refused without a packed tree or when too deep
-int prepare(shray_scene *scene, ShrayQueryScene *q, int *height)
-{
-    int rc = enter_scene(scene, q);
-    if (rc)
-        return rc;
-    rc = check_walkable(*q, 0);
-    if (rc)
-        return rc;
-    rc = tree_height(*q, scene, height);
-    return rc ? rc : check_walkable(*q, *height);
-}
-
 int closest_device(shray_scene *scene, const shray_point *d_points, int64_t count, shray_closest *d_out, hipStream_t stream,
                    DeviceCounters *d_counters)
 {
@@ -73,7 +33,7 @@ int closest_device(shray_scene *scene, const shray_point *d_points, int64_t coun
         return SHRAY_OK;
     ShrayQueryScene q;
     int height = 0;
-    const int rc = prepare(scene, &q, &height);
+    const int rc = enter_walkable_scene(scene, &q, &height);
     return rc ? rc : enqueue_closest(q, height, d_points, (uint64_t)count, d_out, stream, d_counters);
 }
 
@@ -92,7 +52,7 @@ int closest_host(shray_scene *scene, const shray_point *points, int64_t count, s
         return SHRAY_OK;
     ShrayQueryScene q;
     int height = 0;
-    const int rc = prepare(scene, &q, &height);   // (the errors of a scene come before any allocation)
+    const int rc = enter_walkable_scene(scene, &q, &height);   // (the errors of a scene come before any allocation)
     if (rc)
         return rc;
     const size_t n = (size_t)count;

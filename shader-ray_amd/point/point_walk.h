@@ -17,6 +17,7 @@
 #include "device_types.h"
 #include "error_internal.h"
 #include "packed_layout.h"
+#include "packed_walk.h"
 #include "scene_access_internal.h"
 #include "shader_ray_point.h"
 
@@ -25,9 +26,7 @@ namespace {
 using namespace shray;
 
 
-constexpr int kBlock = 64;                          // one wave per workgroup: a lane's stack column is its own
 constexpr uint64_t kPointsPerLaunch = 1ull << 24;   // the grid's threads stay far below 2^32
-constexpr int kOctant = 7;                          // the copy whose entry planes are boxmin and exit planes boxmax
 
 // the stack of one workgroup: (node name, box bound) per level, level-major so that a wave's accesses are consecutive
 inline size_t stack_bytes(int height) { return (size_t)kBlock * (size_t)(height > 0 ? height : 1) * sizeof(uint2); }
@@ -38,10 +37,6 @@ struct PointWork {
     uint64_t count;
     uint64_t first;         // this launch's first point
     DeviceCounters *counters;
-};
-
-struct Box {
-    float lo[3], hi[3];
 };
 
 __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz)
@@ -60,28 +55,6 @@ __device__ __forceinline__ float box_bound(const float p[3], const float lo[3], 
     for (int k = 0; k < 3; k++)
         g[k] = p[k] < lo[k] ? lo[k] - p[k] : (p[k] > hi[k] ? p[k] - hi[k] : 0.0f);
     return dot3(g[0], g[1], g[2], g[0], g[1], g[2]);
-}
-
-struct Record {
-    Box box;
-    uint32_t a, b;
-};
-
-__device__ __forceinline__ Record load_record(const char *copy, uint32_t name)
-{
-    const DeviceNode *n = reinterpret_cast<const DeviceNode *>(copy + ((size_t)name << kNodeNameShift));
-    const float4 w0 = *reinterpret_cast<const float4 *>(n);
-    const float4 w1 = *(reinterpret_cast<const float4 *>(n) + 1);
-    Record r;
-    r.box.lo[0] = w0.x;
-    r.box.lo[1] = w0.y;
-    r.box.hi[0] = w0.z;
-    r.box.hi[1] = w0.w;
-    r.box.lo[2] = w1.x;
-    r.box.hi[2] = w1.y;
-    r.a = __float_as_uint(w1.z);
-    r.b = __float_as_uint(w1.w);
-    return r;
 }
 
 struct Closest {
@@ -261,51 +234,6 @@ __global__ void __launch_bounds__(kBlock) closest_point_kernel(SceneView sc, Poi
             atomicAdd(&c->triangle_tests, s2);
         }
     }
-}
-
-// Edges from the root to the deepest leaf of the packed tree: a function of the topology only, which a refit does not change.
-// A blocking readback of the tree; the libraries keep the result per scene.
-inline int packed_tree_height(const ShrayQueryScene &q, int *height)
-{
-    const uint32_t nodes = q.view.packed_nodes_bytes / (uint32_t)sizeof(DeviceNode);
-    std::vector<DeviceNode> host(nodes);
-    const char *copy = static_cast<const char *>(q.view.packed_nodes) + (size_t)kOctant * q.view.packed_nodes_bytes;
-    HIP_TRY(hipMemcpy(host.data(), copy, q.view.packed_nodes_bytes, hipMemcpyDeviceToHost));
-    // depth-first from the root; a node's name is its byte offset / 8, so its index is name / 4
-    const uint32_t per = (uint32_t)(sizeof(DeviceNode) >> kNodeNameShift);
-    std::vector<std::pair<uint32_t, int>> todo{{q.view.packed_root, 0}};
-    int deepest = 0;
-    uint64_t seen = 0;
-    while (!todo.empty()) {
-        const auto [name, depth] = todo.back();
-        todo.pop_back();
-        if (name % per || name / per >= nodes || ++seen > nodes)
-            return fail(SHRAY_ERR_BAD_TREE, "the packed tree names node %u of %u (or visits a node twice)", name / per, nodes);
-        const DeviceNode &n = host[name / per];
-        if (n.b & kLeafFlag) {
-            const uint64_t end = (uint64_t)n.a + (n.b & ~kLeafFlag);
-            if (end > q.view.triangle_count)
-                return fail(SHRAY_ERR_BAD_TREE, "a leaf of the packed tree names triangles up to %llu of %u", (unsigned long long)end,
-                            q.view.triangle_count);
-            deepest = depth > deepest ? depth : deepest;
-        } else {
-            todo.push_back({n.a & kChildNameMask, depth + 1});
-            todo.push_back({n.b, depth + 1});
-        }
-    }
-    *height = deepest;
-    return SHRAY_OK;
-}
-
-// the walk's refusals of a scene before anything is launched: no packed tree, or one deeper than the LDS stack holds
-inline int check_walkable(const ShrayQueryScene &q, int height)
-{
-    if (!q.packed_ok)
-        return fail(SHRAY_ERR_BAD_TREE, "the scene has no packed tree (closest-point queries walk the packed tree)");
-    if (height > SHRAY_POINT_MAX_HEIGHT)
-        return fail(SHRAY_ERR_BAD_TREE, "the tree is %d levels deep; the closest-point walk's stack holds %d (%zu bytes of LDS a wave)",
-                    height, (int)SHRAY_POINT_MAX_HEIGHT, stack_bytes(SHRAY_POINT_MAX_HEIGHT));
-    return SHRAY_OK;
 }
 
 // `count` > 0 points -> records on `stream`, split over launches (the arguments are checked, the scene is walkable)

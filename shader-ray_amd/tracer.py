@@ -328,6 +328,64 @@ class Scene:
         N.check(N.load_winding().shray_scene_winding_data_download(self._handle, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def trace_all_hits(self, rays, max_hits: int = 8, counts: bool = True, max_leaf_tests: int = 10, counters: bool = False):
+        """All-hits ray queries (include/shader_ray_multihit.h): per ray the number of surfaces it crosses and its first
+        `max_hits` crossings, sorted by (t, triangle), the other slots {tmax, 0, 0, HIT_MISS}.  `rays` as for trace_rays: a
+        RAY_DTYPE array or [n, 6] / [n, 8] float32 takes the blocking host path (shray_trace_all_hits) and returns
+        (hits: HIT_DTYPE [n, max_hits], counts: int32 [n]); a float32 [n, 8] GPU tensor on the scene's device takes the device
+        path (shray_trace_all_hits_device) on the current torch stream and returns (int32 [n, max_hits, 4] tensor of shray_hit
+        records, int32 [n] tensor).  counts=False returns None for the counts and lets the walk skip what cannot reach the
+        first `max_hits` (the same records); max_hits = 0 returns None for the hits.  counters=True (host rays only) also
+        returns the counters of the walk that skips nothing (shray_trace_all_hits_counters)."""
+        lib = N.load_multihit()
+        mp = multihit_params(max_hits, max_leaf_tests)
+        if max_hits == 0 and not counts:
+            raise ValueError("nothing is asked for: max_hits is 0 and counts is False")
+        rays = _host_if_cpu(rays)
+        if _is_torch(rays):
+            import torch
+            if counters:
+                raise ValueError("counters are counted on the host path: pass host rays")
+            if rays.device.index != self.device_index():
+                raise ValueError(f"rays are on {rays.device}, the scene on cuda:{self.device_index()}")
+            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+                raise ValueError("a GPU ray tensor must be float32 [n, 8] (the shray_ray layout)")
+            r = rays.contiguous()
+            hits = torch.empty((len(r), max_hits, 4), dtype=torch.int32, device=r.device) if max_hits > 0 else None
+            cnt = torch.empty(len(r), dtype=torch.int32, device=r.device) if counts else None
+            stream = torch.cuda.current_stream(r.device)
+            r.record_stream(stream)   # (the query reads it after this call returns)
+            N.check(lib.shray_trace_all_hits_device(self._handle, C.byref(mp), C.c_void_p(r.data_ptr()), len(r),
+                                                    C.c_void_p(hits.data_ptr() if hits is not None else None),
+                                                    C.c_void_p(cnt.data_ptr() if counts else None), C.c_void_p(stream.cuda_stream)))
+            return hits, cnt
+        rays = _host_rays(rays)
+        hits = np.empty((len(rays), max_hits), HIT_DTYPE) if max_hits > 0 else None   # (the library refuses a negative one)
+        cnt = np.empty(len(rays), np.int32) if counts else None
+        args = (self._handle, C.byref(mp), rays.ctypes.data_as(C.c_void_p), len(rays),
+                hits.ctypes.data_as(C.c_void_p) if hits is not None else None, cnt.ctypes.data_as(C.c_void_p) if counts else None)
+        if counters:
+            c = N.Counters()
+            N.check(lib.shray_trace_all_hits_counters(*args, C.byref(c)))
+            return hits, cnt, c.as_dict()
+        N.check(lib.shray_trace_all_hits(*args))
+        return hits, cnt
+
+    def trace_all_hits_into(self, rays_ptr: int, count: int, hits_ptr: int, counts_ptr: int = 0, max_hits: int = 8, stream_ptr: int = 0,
+                            max_leaf_tests: int = 10):
+        """Asynchronous all-hits queries on device memory of the scene's device (shray_trace_all_hits_device): `count`
+        shray_ray records at `rays_ptr` -> count * max_hits shray_hit records at `hits_ptr` (0 iff max_hits is 0) and, unless
+        `counts_ptr` is 0, `count` int32 crossing counts there, on a HIP stream (`stream_ptr`)."""
+        mp = multihit_params(max_hits, max_leaf_tests)
+        N.check(N.load_multihit().shray_trace_all_hits_device(self._handle, C.byref(mp), C.c_void_p(rays_ptr), count,
+                                                              C.c_void_p(hits_ptr or None), C.c_void_p(counts_ptr or None),
+                                                              C.c_void_p(stream_ptr)))
+
+    def crossing_counts(self, rays, max_leaf_tests: int = 10):
+        """How many surfaces each ray crosses before its tmax (trace_all_hits with max_hits = 0): int32 [n], numpy for host
+        rays, a tensor for GPU rays."""
+        return self.trace_all_hits(rays, max_hits=0, counts=True, max_leaf_tests=max_leaf_tests)[1]
+
     def primary_hits(self, params: N.FrameParams, width: int, height: int) -> np.ndarray:
         """The hit of every pixel's 1-spp primary ray (shray_primary_hits_device): HIT_DTYPE [height, width], row 0 = bottom."""
         import torch
@@ -495,6 +553,13 @@ def query_params(any_hit: bool = False, max_bvh_iterations: int = 400, max_leaf_
     return qp
 
 
+def multihit_params(max_hits: int = 8, max_leaf_tests: int = 10) -> N.MultihitParams:
+    mp = N.MultihitParams()
+    N.load_multihit().shray_multihit_params_init(C.byref(mp))
+    mp.max_hits, mp.max_leaf_tests = max_hits, max_leaf_tests
+    return mp
+
+
 class DeviceFlat:
     """get_shader_data on the GPU (shray_flatten_device): the flattened arrays of a host-built BVH, resident
     on the device.  `download()` gives a SceneDesc with host pointers (owned by this object)."""
@@ -604,6 +669,19 @@ class DeviceWorld:
     def trace_rays_into(self, rays_ptr: int, count: int, hits_ptr: int, stream_ptr: int = 0, **kwargs):
         """Scene.trace_rays_into on this scene."""
         return self.scene.trace_rays_into(rays_ptr, count, hits_ptr, stream_ptr, **kwargs)
+
+    def trace_all_hits(self, rays, **kwargs):
+        """Scene.trace_all_hits on this scene."""
+        return self.scene.trace_all_hits(rays, **kwargs)
+
+    def trace_all_hits_into(self, rays_ptr: int, count: int, hits_ptr: int, counts_ptr: int = 0, max_hits: int = 8, stream_ptr: int = 0,
+                            **kwargs):
+        """Scene.trace_all_hits_into on this scene."""
+        return self.scene.trace_all_hits_into(rays_ptr, count, hits_ptr, counts_ptr, max_hits, stream_ptr, **kwargs)
+
+    def crossing_counts(self, rays, **kwargs):
+        """Scene.crossing_counts on this scene."""
+        return self.scene.crossing_counts(rays, **kwargs)
 
     def closest_points(self, points, **kwargs):
         """Scene.closest_points on this scene."""
