@@ -2,6 +2,7 @@
 """Measures the class mix bench.py prices the kernel's vector-memory instructions with (roofline.vmem), on the box, over the orbit:
     make -C shader-ray_amd variant VARIANT=uniform HIP_EXTRA="-DSHRAY_DIAGNOSTICS -DSHRAY_DIAG_UNIFORM"
     make -C shader-ray_amd variant VARIANT=khist2 HIP_EXTRA="-DSHRAY_DIAGNOSTICS -DSHRAY_DIAG_KHIST=2 -DSHRAY_DIAG_KHIST_FROM=0"
+    make -C shader-ray_amd variant VARIANT=khist2crowded HIP_EXTRA="-DSHRAY_DIAGNOSTICS -DSHRAY_DIAG_KHIST=2 -DSHRAY_DIAG_KHIST_FROM=32"
     python profiles/make_vmem_mix.py <SQ_INSTS_VMEM_RD per frame> [out.json]
 Two diagnostic builds of THESE sources render the 20 views of bench.py's orbit: how many distinct records the walking lanes of a
 node visit are at (variants/diag_uniform_visit.inc), how many distinct leaves the parked lanes of a leaf stage are in, by rounds
@@ -56,6 +57,10 @@ def main():
     out_path = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "gpurun_out", "vmem_class_mix.json")
     visits, uniform, _, _, _, two, three_four, _ = run("libshray_hip_uniform.so", "nodes")
     rounds = run("libshray_hip_khist2.so", "leaves")[:7]
+    # the rounds of CROWDED stages (more than 32 lanes parked) in one leaf fetch their triangle through the scalar cache
+    # (csrc/leaf_asm.h, SHRAY_LEAF_UNIFORM): no vector-memory instruction
+    scalar_rounds = run("libshray_hip_khist2crowded.so", "leaves")[0]
+    rounds[0] -= scalar_rounds
     more = visits - uniform - two - three_four
     node_insts = 2.0 * (visits - uniform)            # two 16-byte loads per wave-visit the scalar cache does not serve
     tri_insts = 3.0 * sum(rounds)                     # three loads per round of a leaf stage
@@ -70,8 +75,9 @@ def main():
         "build_hash": kernel_source_hash(),
         "build_hash_is": "the product library's device code when the histograms were taken (two diagnostic builds of the same sources)",
         "measured": {"wave_visits_per_frame": visits, "uniform": uniform / visits, "two_records": two / visits, "three_or_four": three_four / visits,
-                     "more": more / visits, "leaf_rounds_per_frame": sum(rounds), "rounds_by_distinct_leaves_1_2_3_4_5to8_9to16_more": r,
-                     "vmem_insts_per_frame": vmem_per_frame},
+                     "more": more / visits, "leaf_rounds_per_frame": sum(rounds) + scalar_rounds, "rounds_by_distinct_leaves_1_2_3_4_5to8_9to16_more": r,
+                     "vmem_insts_per_frame": vmem_per_frame,
+                     "leaf_rounds_through_the_scalar_cache_per_frame": scalar_rounds},
         "kinds": [
             {"name": "node_fetch", "share_of_insts": round(node_insts / vmem_per_frame, 4), "probe_bytes_per_lane": 32,
              "records_per_instruction": {"2": round(two / (visits - uniform), 4), "4": round(three_four / (visits - uniform), 4),

@@ -11,9 +11,113 @@
 // What is rare leaves the statement BEFORE anything is stored, and the round is made by the compiler's form (which holds the
 // true division and the exact leaf range): a determinant outside the three-instruction reciprocal's domain (>= 2^100, or NaN),
 // and a candidate about to be accepted within 2^-19 of an end of its leaf's parked bounds (near_range_end).
+//
+// ONE-LEAF STAGES (round 7, R7.1).  Half of the crowded stages hold one distinct leaf (profiles/r05/leaf_stages_by_distinct_leaves.txt):
+// every testing lane then reads the SAME triangle in every round.  One test per STAGE (v_readfirstlane of leaf_first, one v_cmp_ne,
+// one branch) sends such a stage to a second loop in which the triangle comes through the scalar cache (s_load_dwordx8 + s_load_dword;
+// scalar loads need dword alignment only, and a record is 36 bytes) and its nine words are the arithmetic's SCALAR OPERANDS: every
+// instruction of a round reads at most one of them, which is what the constant bus allows; nothing is moved to lane registers, and
+// Q = T x e0 has v[2:4] to itself.  The next round's triangle is asked for before this round's arithmetic, into a second set of nine
+// scalar registers (two rounds per trip of the loop, one per set); the last round asks for nothing, so nothing is read past the array and
+// nothing is in flight when the statement ends.  The rounds left count DOWN in a scalar register: the subtraction's borrow is both "no
+// next round" tests of a round (SCC survives the round: no other scalar instruction of it writes SCC).  Same operations on the same
+// operands in the same order as the loop beside it.  Per round 67 vector, 2 scalar fetches and 10.5 scalar instructions
+// (the loop beside it, counted the same way: 68, 3 vector fetches, 9).
+// -DSHRAY_LEAF_UNIFORM=0: no stage test, no second loop (the round 6 statement, for A/B builds).
 #pragma once
 
 #include "wave_traversal.h"
+
+#ifndef SHRAY_LEAF_UNIFORM
+#define SHRAY_LEAF_UNIFORM 1
+#endif
+
+// One round of a one-leaf stage.  K: the round's name; V0X ... E1Z: the scalar registers of ITS triangle; BEFORE: scalar bookkeeping
+// in front of the count-down (it may write SCC); AHEAD: the fetches of the next round's triangle into the other set; AGAIN: the
+// branch that ends the round (SCC = this was the last round).
+// %[J]: rounds left after this one (before the subtraction); %[C2]: the leaf's count - 2, so that the round's number is C2 - J.
+#define SHRAY_UNIFORM_LEAF_ROUND(K, V0X, V0Y, V0Z, E0X, E0Y, E0Z, E1X, E1Y, E1Z, BEFORE, AHEAD, AGAIN)                             \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                                                    \
+    BEFORE                                                                                                                         \
+    "s_sub_u32 %[J], %[J], 1\n\t"                           /* SCC: no round after this one */                                     \
+    "s_cbranch_scc1 uq" #K "_%=\n\t"                                                                                              \
+    AHEAD                                                                                                                          \
+    "uq" #K "_%=:\n\t"                                                                                                            \
+    "v_mul_f32 v14, %[Dz], " E1Y "\n\t"                     /* M = cross(e1, D) */                                                 \
+    "v_mul_f32 v15, %[Dy], " E1Z "\n\t"                                                                                           \
+    "v_sub_f32_e32 v11, v14, v15\n\t"                                                                                             \
+    "v_mul_f32 v14, %[Dx], " E1Z "\n\t"                                                                                           \
+    "v_mul_f32 v15, %[Dz], " E1X "\n\t"                                                                                           \
+    "v_sub_f32_e32 v12, v14, v15\n\t"                                                                                             \
+    "v_mul_f32 v14, %[Dy], " E1X "\n\t"                                                                                           \
+    "v_mul_f32 v15, %[Dx], " E1Y "\n\t"                                                                                           \
+    "v_sub_f32_e32 v13, v14, v15\n\t"                                                                                             \
+    "v_mul_f32 v14, " E0X ", v11\n\t"                       /* det = dot(e0, M) */                                                 \
+    "v_mul_f32 v15, " E0Y ", v12\n\t"                                                                                             \
+    "v_add_f32_e32 v14, v14, v15\n\t"                                                                                             \
+    "v_mul_f32 v15, " E0Z ", v13\n\t"                                                                                             \
+    "v_add_f32_e32 v16, v15, v14\n\t"                                                                                             \
+    "v_cmpx_nlt_f32_e64 vcc, |v16|, %[eps]\n\t"                                                                                   \
+    "v_rcp_f32_e32 v17, v16\n\t"                                                                                                  \
+    "v_cmp_nlt_f32_e64 vcc, |v16|, %[big]\n\t"                                                                                    \
+    "v_fma_f32 v14, -v16, v17, 1.0\n\t"                                                                                           \
+    "v_fmac_f32_e32 v17, v14, v17\n\t"                                                                                            \
+    "s_cbranch_vccnz uslow_%=\n\t"                                                                                                \
+    "v_sub_f32 v18, %[Px], " V0X "\n\t"                     /* T = P - v0 */                                                       \
+    "v_sub_f32 v19, %[Py], " V0Y "\n\t"                                                                                           \
+    "v_sub_f32 v20, %[Pz], " V0Z "\n\t"                                                                                           \
+    "v_mul_f32 v14, v19, " E0Z "\n\t"                       /* Q = cross(T, e0) */                                                 \
+    "v_mul_f32 v15, v20, " E0Y "\n\t"                                                                                             \
+    "v_sub_f32_e32 v2, v14, v15\n\t"                                                                                              \
+    "v_mul_f32 v14, v20, " E0X "\n\t"                                                                                             \
+    "v_mul_f32 v15, v18, " E0Z "\n\t"                                                                                             \
+    "v_sub_f32_e32 v3, v14, v15\n\t"                                                                                              \
+    "v_mul_f32 v14, v18, " E0Y "\n\t"                                                                                             \
+    "v_mul_f32 v15, v19, " E0X "\n\t"                                                                                             \
+    "v_sub_f32_e32 v4, v14, v15\n\t"                                                                                              \
+    "v_mul_f32 v14, " E1X ", v2\n\t"                        /* d = -dot(e1, Q) / det */                                            \
+    "v_mul_f32 v15, " E1Y ", v3\n\t"                                                                                              \
+    "v_add_f32_e32 v14, v14, v15\n\t"                                                                                             \
+    "v_mul_f32 v15, " E1Z ", v4\n\t"                                                                                              \
+    "v_add_f32_e32 v14, v15, v14\n\t"                                                                                             \
+    "v_mul_f32_e64 v16, v17, -v14\n\t"                                                                                            \
+    "v_min_f32_e32 v14, %[HT], %[LR1]\n\t"                                                                                        \
+    "v_cmpx_nlt_f32_e32 v16, %[LR0]\n\t"                                                                                          \
+    "v_cmpx_ngt_f32_e32 v16, v14\n\t"                                                                                             \
+    "s_cbranch_execz un" #K "_%=\n\t"                                                                                             \
+    "v_mul_f32_e32 v14, v18, v11\n\t"                       /* u */                                                                \
+    "v_mul_f32_e32 v15, v19, v12\n\t"                                                                                             \
+    "v_add_f32_e32 v14, v14, v15\n\t"                                                                                             \
+    "v_mul_f32_e32 v15, v20, v13\n\t"                                                                                             \
+    "v_add_f32_e32 v14, v15, v14\n\t"                                                                                             \
+    "v_mul_f32_e32 v14, v14, v17\n\t"                                                                                             \
+    "v_cmpx_ngt_f32_e32 0, v14\n\t"                                                                                               \
+    "v_cmpx_nlt_f32_e32 1.0, v14\n\t"                                                                                             \
+    "v_mul_f32_e32 v15, %[Dx], v2\n\t"                      /* w */                                                                \
+    "v_mul_f32_e32 v11, %[Dy], v3\n\t"                                                                                            \
+    "v_add_f32_e32 v15, v15, v11\n\t"                                                                                             \
+    "v_mul_f32_e32 v11, %[Dz], v4\n\t"                                                                                            \
+    "v_add_f32_e32 v15, v11, v15\n\t"                                                                                             \
+    "v_mul_f32_e32 v15, v15, v17\n\t"                                                                                             \
+    "v_add_f32_e32 v11, v14, v15\n\t"                                                                                             \
+    "v_cmpx_ngt_f32_e32 0, v15\n\t"                                                                                               \
+    "v_cmpx_nlt_f32_e32 1.0, v11\n\t"                                                                                             \
+    "s_cbranch_execz un" #K "_%=\n\t"                                                                                             \
+    "v_mul_f32_e32 v11, 0x3f7fffe0, v16\n\t"                /* near_range_end: two branches, SCC stays */                          \
+    "v_mul_f32_e32 v12, 0x3f800010, v16\n\t"                                                                                      \
+    "v_cmp_lt_f32_e32 vcc, v11, %[LR0]\n\t"                                                                                       \
+    "s_cbranch_vccnz uslow_%=\n\t"                                                                                                \
+    "v_cmp_gt_f32_e32 vcc, v12, %[LR1]\n\t"                                                                                       \
+    "s_cbranch_vccnz uslow_%=\n\t"                                                                                                \
+    "v_subrev_u32_e32 v11, %[J], %[LF]\n\t"                 /* the hit: triangle leaf_first + (C2 - J) */                          \
+    "v_add_u32_e32 v11, %[C2], v11\n\t"                                                                                           \
+    "v_cvt_f32_u32_e32 %[HW], v11\n\t"                                                                                            \
+    "v_mov_b32_e32 %[HT], v16\n\t"                                                                                                \
+    "v_mov_b32_e32 %[HU], v14\n\t"                                                                                                \
+    "v_mov_b32_e32 %[HV], v15\n"                                                                                                  \
+    "un" #K "_%=:\n\t"                                                                                                            \
+    "s_mov_b64 exec, %[sP]\n\t"                                                                                                   \
+    AGAIN
 
 namespace shray {
 
@@ -28,12 +132,47 @@ __device__ __forceinline__ void leaf_loop_scheduled(const SceneView &sc, LaneTra
     for (;;) {
         uint32_t reason, j_next;
         unsigned long long saved, other;
+#if SHRAY_LEAF_UNIFORM
+        unsigned long long testing;
+        uint32_t offset, count_less_two;
+#endif
         asm volatile(
             "s_mov_b64 %[saved], exec\n\t"
             "v_readfirstlane_b32 %[J], %[J0]\n\t"         // (the round counter: uniform, handed over in a lane register)
             "s_nop 1\n\t"                                  // (a VALU-written SGPR read by a VALU: two wait states)
             "v_cmpx_lt_u32_e32 %[J], %[MINE]\n\t"
-            "s_cbranch_execz ldone_%=\n"
+            "s_cbranch_execz ldone_%=\n\t"
+#if SHRAY_LEAF_UNIFORM
+            // the stage's test: every testing lane in one leaf (then their counts are one count, too)
+            "v_readfirstlane_b32 %[reason], %[LF]\n\t"
+            "v_readfirstlane_b32 %[C2], %[MINE]\n\t"
+            "s_nop 0\n\t"                                  // (a VALU-written SGPR read by a VALU: two wait states)
+            "v_cmp_ne_u32_e32 vcc, %[reason], %[LF]\n\t"
+            "s_cbranch_vccnz lround_%=\n\t"
+            "s_mov_b64 %[sP], exec\n\t"
+            "s_add_u32 %[reason], %[reason], %[J]\n\t"
+            "s_mul_i32 %[sO], %[reason], 36\n\t"            // round j's triangle: a byte offset into packed_tris
+            "s_load_dwordx8 s[64:71], %[base], %[sO]\n\t"
+            "s_load_dword s54, %[base], %[sO] offset:32\n\t"
+            "s_sub_u32 %[C2], %[C2], 2\n\t"
+            "s_sub_u32 %[J], %[C2], %[J]\n\t"
+            "s_add_u32 %[J], %[J], 1\n"                      // rounds left after round j: count - 1 - j
+            "uround_%=:\n\t"
+            SHRAY_UNIFORM_LEAF_ROUND(0, "s64", "s65", "s66", "s67", "s68", "s69", "s70", "s71", "s54", "",
+                                     "s_load_dwordx8 s[56:63], %[base], %[sO] offset:36\n\t"
+                                     "s_load_dword s55, %[base], %[sO] offset:68\n",
+                                     "s_cbranch_scc1 ldone_%=\n\t")
+            SHRAY_UNIFORM_LEAF_ROUND(1, "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s55",
+                                     "s_add_u32 %[sO], %[sO], 72\n\t",
+                                     "s_load_dwordx8 s[64:71], %[base], %[sO]\n\t"
+                                     "s_load_dword s54, %[base], %[sO] offset:32\n",
+                                     "s_cbranch_scc0 uround_%=\n\t")
+            "s_branch ldone_%=\n"
+            "uslow_%=:\n\t"
+            "s_sub_u32 %[J], %[C2], %[J]\n\t"               // the round's number, for the compiler's round
+            "s_waitcnt lgkmcnt(0)\n\t"                      // (the next triangle may be on its way: its registers are not ours after this)
+            "s_branch lslow_%=\n"
+#endif
             "lround_%=:\n\t"
             "global_load_dwordx4 v[2:5], %[W], %[base]\n\t"
             "global_load_dwordx4 v[6:9], %[W], %[base] offset:16\n\t"
@@ -134,11 +273,18 @@ __device__ __forceinline__ void leaf_loop_scheduled(const SceneView &sc, LaneTra
             "s_mov_b64 exec, %[saved]\n\t"
             : [HT] "+v"(t.hit.t), [HW] "+v"(t.hit.which), [HU] "+v"(t.hit.bu), [HV] "+v"(t.hit.bv), [W] "+v"(where), [J] "=&s"(j_next),
               [saved] "=&s"(saved), [other] "=&s"(other), [reason] "=&s"(reason)
+#if SHRAY_LEAF_UNIFORM
+              , [sP] "=&s"(testing), [sO] "=&s"(offset), [C2] "=&s"(count_less_two)
+#endif
             : [Px] "v"(t.P.x), [Py] "v"(t.P.y), [Pz] "v"(t.P.z), [Dx] "v"(t.D.x), [Dy] "v"(t.D.y), [Dz] "v"(t.D.z), [LR0] "v"(t.leaf_r0),
               [LR1] "v"(t.leaf_r1), [LF] "v"(t.leaf_first), [MINE] "v"(mine), [base] "s"(sc.packed_tris), [eps] "s"(0.0000001f),
               [big] "s"(0x1p100f), [J0] "v"(j)
             : "vcc", "scc", "memory", "v2", "v3", "v4", "v5", "v6", "v7", "v8", "v9", "v10", "v11", "v12", "v13", "v14", "v15", "v16",
-              "v17", "v18", "v19", "v20");
+              "v17", "v18", "v19", "v20"
+#if SHRAY_LEAF_UNIFORM
+              , "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69", "s70", "s71"
+#endif
+            );
         // (an asm statement's results count as divergent whatever register class they are in: say they are not)
         if (__builtin_amdgcn_readfirstlane((int)reason) == 0)
             return;
