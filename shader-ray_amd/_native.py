@@ -19,6 +19,8 @@ POINT_LIB = os.path.join(PKG_DIR, "libshray_point.so")
 SDF_LIB = os.path.join(PKG_DIR, "libshray_sdf.so")
 WINDING_LIB = os.path.join(PKG_DIR, "libshray_winding.so")
 MULTIHIT_LIB = os.path.join(PKG_DIR, "libshray_multihit.so")
+# SHRAY_NEAR_LIB selects an experiment build of the same library (profiles/near_bench.py --ab); unset in normal use
+NEAR_LIB = os.environ.get("SHRAY_NEAR_LIB") or os.path.join(PKG_DIR, "libshray_near.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
 HIP_LIB = os.environ.get("SHRAY_HIP_LIB") or os.path.join(PKG_DIR, "libshray_hip.so")
 
@@ -387,6 +389,23 @@ MULTIHIT_SYMBOLS = [
                                                 C.POINTER(Counters)]),
 ]
 
+# include/shader_ray_near.h --------------------------------------------------------------------------------
+NEAR_MAX = 64
+
+
+class NearParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_near", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+NEAR_SYMBOLS = [
+    ("shray_near_params_init", None, [C.POINTER(NearParams)]),
+    ("shray_near_triangles_device", C.c_int, [C.c_void_p, C.POINTER(NearParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    ("shray_near_triangles", C.c_int, [C.c_void_p, C.POINTER(NearParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("shray_near_triangles_counters", C.c_int, [C.c_void_p, C.POINTER(NearParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                C.POINTER(Counters)]),
+]
+
 _host = None
 _hip = None
 _clients = {}   # path -> the loaded client library of libshray_hip.so
@@ -478,6 +497,11 @@ def load_winding():
 def load_multihit():
     """Loads the all-hits ray-query library (libshray_multihit.so)."""
     return _load_client(MULTIHIT_LIB, MULTIHIT_SYMBOLS)
+
+
+def load_near():
+    """Loads the within-radius query library (libshray_near.so)."""
+    return _load_client(NEAR_LIB, NEAR_SYMBOLS)
 
 
 def check_dist(code: int):

@@ -386,6 +386,60 @@ class Scene:
         rays, a tensor for GPU rays."""
         return self.trace_all_hits(rays, max_hits=0, counts=True, max_leaf_tests=max_leaf_tests)[1]
 
+    def triangles_within(self, points, max_near: int = 8, counts: bool = True, counters: bool = False):
+        """Within-radius queries (include/shader_ray_near.h): per point the number of triangles whose closest point lies
+        within its max_dist2 and the nearest `max_near` of them as shray_closest records, sorted by (dist2, triangle), the
+        other slots miss records.  `points` as for closest_points: a POINT_DTYPE array or [n, 3] / [n, 4] float32 takes the
+        blocking host path (shray_near_triangles) and returns (records: CLOSEST_DTYPE [n, max_near], counts: int32 [n]); a
+        float32 [n, 3] / [n, 4] GPU tensor on the scene's device takes the device path (shray_near_triangles_device) on the
+        current torch stream and returns (int32 [n, max_near, 8] tensor of shray_closest records, int32 [n] tensor).
+        counts=False returns None for the counts and lets the walk skip what cannot reach the nearest `max_near` (the same
+        records); max_near = 0 returns None for the records.  counters=True (host points only) also returns the counters of
+        the walk that prunes only by max_dist2 (shray_near_triangles_counters)."""
+        lib = N.load_near()
+        np_ = near_params(max_near)
+        if max_near == 0 and not counts:
+            raise ValueError("nothing is asked for: max_near is 0 and counts is False")
+        points = _host_if_cpu(points)
+        if _is_torch(points):
+            import torch
+            if counters:
+                raise ValueError("counters are counted on the host path: pass host points")
+            pts = self._device_points(points)
+            out = torch.empty((len(pts), max_near, 8), dtype=torch.int32, device=pts.device) if max_near > 0 else None
+            cnt = torch.empty(len(pts), dtype=torch.int32, device=pts.device) if counts else None
+            stream = torch.cuda.current_stream(pts.device)
+            pts.record_stream(stream)   # (the query reads it after this call returns)
+            N.check(lib.shray_near_triangles_device(self._handle, C.byref(np_), C.c_void_p(pts.data_ptr()), len(pts),
+                                                    C.c_void_p(out.data_ptr() if out is not None else None),
+                                                    C.c_void_p(cnt.data_ptr() if counts else None), C.c_void_p(stream.cuda_stream)))
+            return out, cnt
+        pts = _host_points(points)
+        out = np.empty((len(pts), max_near), CLOSEST_DTYPE) if max_near > 0 else None   # (the library refuses a negative one)
+        cnt = np.empty(len(pts), np.int32) if counts else None
+        args = (self._handle, C.byref(np_), pts.ctypes.data_as(C.c_void_p), len(pts),
+                out.ctypes.data_as(C.c_void_p) if out is not None else None, cnt.ctypes.data_as(C.c_void_p) if counts else None)
+        if counters:
+            c = N.Counters()
+            N.check(lib.shray_near_triangles_counters(*args, C.byref(c)))
+            return out, cnt, c.as_dict()
+        N.check(lib.shray_near_triangles(*args))
+        return out, cnt
+
+    def triangles_within_into(self, points_ptr: int, count: int, out_ptr: int, counts_ptr: int = 0, max_near: int = 8, stream_ptr: int = 0):
+        """Asynchronous within-radius queries on device memory of the scene's device (shray_near_triangles_device): `count`
+        shray_point records at `points_ptr` -> count * max_near shray_closest records at `out_ptr` (0 iff max_near is 0) and,
+        unless `counts_ptr` is 0, `count` int32 near counts there, on a HIP stream (`stream_ptr`)."""
+        np_ = near_params(max_near)
+        N.check(N.load_near().shray_near_triangles_device(self._handle, C.byref(np_), C.c_void_p(points_ptr), count,
+                                                          C.c_void_p(out_ptr or None), C.c_void_p(counts_ptr or None),
+                                                          C.c_void_p(stream_ptr)))
+
+    def near_counts(self, points):
+        """How many triangles lie within each point's max_dist2 (triangles_within with max_near = 0): int32 [n], numpy for
+        host points, a tensor for GPU points."""
+        return self.triangles_within(points, max_near=0, counts=True)[1]
+
     def primary_hits(self, params: N.FrameParams, width: int, height: int) -> np.ndarray:
         """The hit of every pixel's 1-spp primary ray (shray_primary_hits_device): HIT_DTYPE [height, width], row 0 = bottom."""
         import torch
@@ -560,6 +614,13 @@ def multihit_params(max_hits: int = 8, max_leaf_tests: int = 10) -> N.MultihitPa
     return mp
 
 
+def near_params(max_near: int = 8) -> N.NearParams:
+    np_ = N.NearParams()
+    N.load_near().shray_near_params_init(C.byref(np_))
+    np_.max_near = max_near
+    return np_
+
+
 class DeviceFlat:
     """get_shader_data on the GPU (shray_flatten_device): the flattened arrays of a host-built BVH, resident
     on the device.  `download()` gives a SceneDesc with host pointers (owned by this object)."""
@@ -690,6 +751,18 @@ class DeviceWorld:
     def closest_points_into(self, points_ptr: int, count: int, out_ptr: int, stream_ptr: int = 0):
         """Scene.closest_points_into on this scene."""
         return self.scene.closest_points_into(points_ptr, count, out_ptr, stream_ptr)
+
+    def triangles_within(self, points, **kwargs):
+        """Scene.triangles_within on this scene."""
+        return self.scene.triangles_within(points, **kwargs)
+
+    def triangles_within_into(self, points_ptr: int, count: int, out_ptr: int, counts_ptr: int = 0, max_near: int = 8, stream_ptr: int = 0):
+        """Scene.triangles_within_into on this scene."""
+        return self.scene.triangles_within_into(points_ptr, count, out_ptr, counts_ptr, max_near, stream_ptr)
+
+    def near_counts(self, points):
+        """Scene.near_counts on this scene."""
+        return self.scene.near_counts(points)
 
     def signed_distance(self, points, **kwargs):
         """Scene.signed_distance on this scene."""
