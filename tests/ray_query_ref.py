@@ -140,6 +140,33 @@ def trace(scene, origins, directions, tmax, max_bvh_iterations: int = 400, max_l
     return hits, counts
 
 
+# exact_div.h's range predicates, restated on the raw exponent field (NaN and inf fail every one of them; a denormal's field
+# is 0, below every range).  The walk above divides; these only say which form of the slab test the library may choose.
+def magnitude_in(v, lo_exp: int, hi_exp: int):
+    """2^lo_exp <= |v| < 2^(hi_exp + 1)"""
+    e = ((np.ascontiguousarray(v, F).view(np.uint32) >> 23) & 0xff).astype(np.int64) - 127
+    return (e >= lo_exp) & (e <= hi_exp)
+
+
+def divisor_in_range(b):
+    return magnitude_in(b, -40, 19)
+
+
+def coordinate_in_range(c):
+    return (np.asarray(c, F) == 0) | magnitude_in(c, -70, 59)
+
+
+def scene_exact_div_ok(boxmin, boxmax) -> int:
+    """the scene's flag: every box coordinate is 0 or has magnitude in [2^-70, 2^60)"""
+    return int(coordinate_in_range(boxmin).all() and coordinate_in_range(boxmax).all())
+
+
+def fast_division(flag: int, origins, directions):
+    """bool [n]: the ray may take div_by_constant4 (wave_traversal.h: lane_begin, multihit.hip: make_slab); else it divides"""
+    o, d = np.asarray(origins, F).reshape(-1, 3), np.asarray(directions, F).reshape(-1, 3)
+    return bool(flag) & divisor_in_range(d).all(1) & coordinate_in_range(o).all(1)
+
+
 def xform(m, v, w):
     """trace_common.h: xform -- column-major mat4 times (v, w), float32, in the shader's order ([n, 3] v)."""
     m = np.asarray(m, F).reshape(16)
