@@ -19,6 +19,7 @@ POINT_LIB = os.path.join(PKG_DIR, "libshray_point.so")
 SDF_LIB = os.path.join(PKG_DIR, "libshray_sdf.so")
 WINDING_LIB = os.path.join(PKG_DIR, "libshray_winding.so")
 MULTIHIT_LIB = os.path.join(PKG_DIR, "libshray_multihit.so")
+INSTANCE_MULTIHIT_LIB = os.path.join(PKG_DIR, "libshray_instance_multihit.so")
 # SHRAY_NEAR_LIB selects an experiment build of the same library (profiles/near_bench.py --ab); unset in normal use
 NEAR_LIB = os.environ.get("SHRAY_NEAR_LIB") or os.path.join(PKG_DIR, "libshray_near.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
@@ -406,6 +407,16 @@ NEAR_SYMBOLS = [
                                                 C.POINTER(Counters)]),
 ]
 
+# include/shader_ray_instance_multihit.h -------------------------------------------------------------------
+INSTANCE_MULTIHIT_SYMBOLS = [
+    ("shray_trace_instances_all_hits_device", C.c_int, [C.c_void_p, C.POINTER(MultihitParams), C.c_void_p, C.c_int64, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("shray_trace_instances_all_hits", C.c_int, [C.c_void_p, C.POINTER(MultihitParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]),
+    ("shray_trace_instances_all_hits_counters", C.c_int, [C.c_void_p, C.POINTER(MultihitParams), C.c_void_p, C.c_int64, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
+]
+
 _host = None
 _hip = None
 _clients = {}   # path -> the loaded client library of libshray_hip.so
@@ -502,6 +513,11 @@ def load_multihit():
 def load_near():
     """Loads the within-radius query library (libshray_near.so)."""
     return _load_client(NEAR_LIB, NEAR_SYMBOLS)
+
+
+def load_instance_multihit():
+    """Loads the instanced all-hits library (libshray_instance_multihit.so: depends on libshray_instance.so too)."""
+    return _load_client(INSTANCE_MULTIHIT_LIB, INSTANCE_MULTIHIT_SYMBOLS)
 
 
 def check_dist(code: int):

@@ -27,23 +27,14 @@
 #include "query_common.h"
 #include "scene_access_internal.h"
 #include "shader_ray_instance.h"
+#include "top_level.h"
 
 using namespace shray;
 
 namespace {
 
-constexpr int kTopStack = 32;              // per-wave top-level stack entries: the depth is at most ceil(log2 2^20) = 20
-constexpr uint32_t kLeafBit = 0x80000000u; // a node link: leaf | instance, or axis << 29 | first child (the second follows it)
 // The cull's margin factor: 128 ulps of 1 times the instance's condition ||A||inf * ||W||inf
 constexpr double kMarginUlps = 128.0 / 16777216.0;
-
-// A top-level node, two float4: (lo.xyz, margin factor k) and (hi.xyz, link bits).  A lane widens the box by k * |P|inf more.
-struct TopNode {
-    float lo[3], k;
-    float hi[3];
-    uint32_t link;
-};
-static_assert(sizeof(TopNode) == 32, "two float4");
 
 // What a launch reads besides the rays: every pointer is __restrict__ in the kernel's arguments, so that the views come in
 // by scalar loads (the traversal's inline asm takes their packed-array pointers as "s" operands)
@@ -59,41 +50,6 @@ void free_device(SetDevice &d)
         if (p)
             (void)hipFree(p);
     d = SetDevice{};
-}
-
-// one lane's slab test of a top-level box over [0, limit], widened by `pad`; a NaN quotient (0 * inf at a plane) enters
-__device__ __forceinline__ bool enters_box(const float4 &a, const float4 &b, const V3 &P, const V3 &D, float pad, float limit)
-{
-    float tn = 0.0f, tf = limit;
-    const float lo[3] = {a.x, a.y, a.z}, hi[3] = {b.x, b.y, b.z}, p[3] = {P.x, P.y, P.z}, d[3] = {D.x, D.y, D.z};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float q0 = ((lo[c] - pad) - p[c]) / d[c], q1 = ((hi[c] + pad) - p[c]) / d[c];
-        if (q0 == q0 && q1 == q1) {
-            tn = fmaxf(tn, fminf(q0, q1));
-            tf = fminf(tf, fmaxf(q0, q1));
-        }
-    }
-    return tn <= tf;
-}
-
-// row r of W applied to v (w: also add the translation): the products of nonzero entries only, left to right
-__device__ __forceinline__ float object_row(const float4 &row, const V3 &v, bool w)
-{
-    float acc = 0.0f;
-    bool any = false;
-    const float m[3] = {row.x, row.y, row.z}, x[3] = {v.x, v.y, v.z};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if (m[c] != 0.0f) {
-            const float prod = m[c] * x[c];
-            acc = any ? acc + prod : prod;
-            any = true;
-        }
-    }
-    if (w && row.w != 0.0f)
-        acc = any ? acc + row.w : row.w;
-    return acc;
 }
 
 // One-wave workgroups, as query_stack_kernel.  COUNT: the counting instance (closest-hit walks, the compiler's node stage).
@@ -662,6 +618,7 @@ struct DeviceUpdate {
 
 struct shray_instance_set {
     std::vector<shray_scene *> scenes;
+    std::vector<shray_scene *> distinct;    // the member scenes by scene slot (prepare's: first appearance)
     Prepared host;
     SetDevice dev;
     std::unique_ptr<DeviceUpdate> update;   // the device update's state, once one was made
@@ -968,6 +925,9 @@ int shray_instance_set_create(const shray_instance *instances, int32_t count, sh
     }
     shray_instance_set *set = new shray_instance_set;
     set->scenes = std::move(scenes);
+    for (shray_scene *s : set->scenes)
+        if (std::find(set->distinct.begin(), set->distinct.end(), s) == set->distinct.end())
+            set->distinct.push_back(s);
     const int rc = make_set(set->scenes, transforms.data(), set->host, set->dev);
     if (rc) {
         delete set;
@@ -1073,6 +1033,22 @@ int shrayi_instance_set_arrays(const shray_instance_set *set, void *nodes, void 
         HIP_TRY(hipMemcpy(nodes, set->dev.nodes, (2 * n - 1) * sizeof(TopNode), hipMemcpyDeviceToHost));
     if (records)
         HIP_TRY(hipMemcpy(records, set->dev.records, 4 * n * sizeof(float4), hipMemcpyDeviceToHost));
+    return SHRAY_OK;
+}
+
+// For libshray_instance_multihit.so, not in the header (top_level.h): the set's device arrays as the next launch reads them
+// and its distinct member scenes.  Device pointers: nothing is copied, nothing waited for, no device touched.
+int shrayi_instance_set_device_arrays(const shray_instance_set *set, ShrayInstanceSetDevice *out)
+{
+    if (!set || !out)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "set or out is NULL");
+    out->nodes = set->dev.nodes;
+    out->records = set->dev.records;
+    out->views = set->dev.views;
+    out->scenes = set->distinct.data();
+    out->count = (int32_t)set->scenes.size();
+    out->scene_count = (int32_t)set->distinct.size();
+    out->device = set->host.device;
     return SHRAY_OK;
 }
 

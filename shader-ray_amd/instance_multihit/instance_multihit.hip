@@ -1,0 +1,280 @@
+// instance_multihit.hip -- include/shader_ray_instance_multihit.h: every crossing of a world-space ray with a set of placed
+// scenes, counted, the first K kept in order with their instances.
+//
+// One lane per ray in one-wave workgroups.  The wave walks the set's top level uniformly, as instance.hip's kernel does
+// (instance/top_level.h: the widened slab test, the untested root, near children first by the first live lane's signs, a
+// 32-word LDS stack read with readfirstlane); at a leaf the lanes whose rays enter its box move their rays into the
+// instance's object space and each runs the all-hits walk of that scene (multihit/all_hits_walk.h) into its own K best,
+// which carry the instance index as a fifth field.  The cull limit of a lane is its tmax, or, in the form that is not asked
+// for counts, the K-th smallest t it holds: the same t_K that prunes the walks inside the scenes.
+// This library is built apart from libshray_hip.so, libshray_instance.so and libshray_multihit.so, so their code objects do
+// not change.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "all_hits_walk.h"
+#include "client_internal.h"
+#include "packed_walk.h"
+#include "shader_ray_instance_multihit.h"
+#include "top_level.h"
+#include "trace_common.h"
+
+using namespace shray;
+
+namespace {
+
+constexpr uint64_t kRaysPerLaunch = 1ull << 24;   // the grid's threads stay far below 2^32
+
+struct SetWork {
+    const float4 *rays;    // 2 float4 per ray, world space
+    float4 *hits;          // k per ray: (t, u, v, triangle bits); not touched when k == 0
+    int32_t *instances;    // k per ray, or nullptr (never nullptr for the form that keeps its K best in memory, k > 0)
+    int32_t *counts;       // one per ray, or nullptr
+    uint64_t count;
+    uint64_t first;        // this launch's first ray
+    int32_t k;             // records per ray
+    int32_t max_leaf_tests;
+    int32_t stack_levels;  // the tallest member scene's height (at least 1): the top-level stack follows the walk's columns
+    DeviceCounters *counters;
+};
+
+// One lane per ray.  SLOTS, PRUNE, COUNT: as all_hits_kernel's (multihit/multihit.hip).  The pointers are __restrict__ so that
+// a leaf's record and its SceneView come in by scalar loads.
+template <int SLOTS, bool PRUNE, bool COUNT>
+__global__ void __launch_bounds__(kBlock) instance_all_hits_kernel(SetWork w, const TopNode *__restrict__ nodes,
+                                                                   const float4 *__restrict__ records,
+                                                                   const SceneView *__restrict__ views)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+    uint32_t *column = lds_stack + threadIdx.x;                      // node names, level-major
+    uint32_t *top = lds_stack + (size_t)kBlock * w.stack_levels;     // the wave's top-level stack
+    const uint64_t index = w.first + (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool live = index < w.count;
+    float4 ra = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rb = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
+    if (live) {
+        ra = w.rays[2 * index];
+        rb = w.rays[2 * index + 1];
+    }
+    const V3 P = mk(ra.x, ra.y, ra.z), D = mk(rb.x, rb.y, rb.z);
+    const float tmax = ra.w;
+    const bool traced = live && tmax > 0.0f;   // (false for NaN)
+    KBest<SLOTS, true> best;
+    best.init(tmax, w.k, w.hits + index * (uint64_t)w.k, w.instances + index * (uint64_t)w.k, live);   // (this ray's own slots)
+    RayCounters rc = {0, 0, 0, 0, 0, 0, 0};
+    const float pmax = fmaxf(fabsf(P.x), fmaxf(fabsf(P.y), fabsf(P.z)));
+    const unsigned long long first = __builtin_amdgcn_ballot_w64(traced);
+    if (first) {
+        // near children first by the first live lane's direction signs (the walk's order affects its speed only)
+        const uint32_t signs = (uint32_t)__builtin_amdgcn_readlane((int)((D.x >= 0.0f ? 1u : 0u) | (D.y >= 0.0f ? 2u : 0u) |
+                                                                          (D.z >= 0.0f ? 4u : 0u)),
+                                                                    (int)__builtin_ctzll(first));
+        uint32_t node = 0;
+        int sp = 0;
+        for (;;) {
+            const float4 a = reinterpret_cast<const float4 *>(nodes)[2u * node];
+            const float4 b = reinterpret_cast<const float4 *>(nodes)[2u * node + 1u];
+            // The root is not tested: a set of one instance culls nothing, so its walks are the plain query's.  A lane's
+            // limit: nothing beyond tmax is accepted; nothing beyond t_K can enter the first k (a box that begins AT t_K
+            // is entered: enters_box keeps tn <= limit, and a lower instance wins a tie there)
+            const bool enters = traced && (node == 0u || enters_box(a, b, P, D, a.w * pmax, PRUNE ? best.tk : tmax));
+            if (__builtin_amdgcn_ballot_w64(enters)) {
+                const uint32_t link = __float_as_uint(b.w);
+                if (!(link & kLeafBit)) {
+                    const uint32_t left = link & 0x1fffffffu;
+                    const bool low_first = (signs >> (link >> 29)) & 1u;
+                    top[sp++] = low_first ? left + 1u : left;   // the far child waits (every lane writes the same word)
+                    node = low_first ? left : left + 1u;
+                    continue;
+                }
+                const int inst = (int)(link & ~kLeafBit);
+                const float4 *rec = records + 4u * (uint32_t)inst;
+                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
+                const SceneView &sc = views[__float_as_uint(rec[3].x)];
+                if (enters) {
+                    const V3 Po = mk(object_row(r0, P, true), object_row(r1, P, true), object_row(r2, P, true));
+                    const V3 Do = mk(object_row(r0, D, false), object_row(r1, D, false), object_row(r2, D, false));
+                    all_hits_walk<SLOTS, PRUNE, true>(sc, Po, Do, tmax, w.max_leaf_tests, inst, column, best, rc);
+                }
+            }
+            if (sp == 0)
+                break;
+            node = (uint32_t)__builtin_amdgcn_readfirstlane((int)top[--sp]);
+        }
+    }
+    if (live) {
+        best.store(w.instances ? w.instances + index * (uint64_t)w.k : nullptr);
+        if (w.counts)
+            w.counts[index] = best.n;
+    }
+    if (COUNT)
+        add_counters(rc, w.counters);   // (every lane of the wave is here)
+}
+
+int check_params(const shray_multihit_params *mp)
+{
+    if (!mp)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "multihit params are NULL");
+    if (mp->struct_size != sizeof(shray_multihit_params))
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "shray_multihit_params.struct_size is %u, this library expects %zu", mp->struct_size,
+                    sizeof(shray_multihit_params));
+    if (mp->max_hits < 0 || mp->max_hits > SHRAY_MULTIHIT_MAX || mp->max_leaf_tests < 0 || mp->max_leaf_tests > (1 << 24) || mp->reserved != 0)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "multihit params out of range (max_hits %d of 0 .. %d, max_leaf_tests %d, reserved %d)",
+                    mp->max_hits, (int)SHRAY_MULTIHIT_MAX, mp->max_leaf_tests, mp->reserved);
+    return SHRAY_OK;
+}
+
+// the checks every form makes before it touches a set or a device
+int check_query(shray_instance_set *set, const shray_multihit_params *mp, const void *rays, int64_t count, const void *hits, const void *counts)
+{
+    const int rc = check_params(mp);
+    if (rc)
+        return rc;
+    if (count < 0)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "negative ray count %lld", (long long)count);
+    if (!set || !rays)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "set or rays is NULL");
+    if (mp->max_hits > 0 && !hits)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "hits is NULL with max_hits %d", mp->max_hits);
+    if (mp->max_hits == 0 && !counts)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "nothing is asked for: max_hits is 0 and counts is NULL");
+    return SHRAY_OK;
+}
+
+// the set's arrays on its device, and the height of its tallest member tree (each member's read back once per scene)
+int enter_set(shray_instance_set *set, ShrayInstanceSetDevice *d, int *height)
+{
+    int rc = shrayi_instance_set_device_arrays(set, d);
+    if (rc)
+        return rc;
+    if ((rc = use_device(d->device)))
+        return rc;
+    *height = 0;
+    for (int32_t s = 0; s < d->scene_count; s++) {
+        ShrayQueryScene q;
+        int h = 0;
+        if ((rc = shrayi_scene_query_view(d->scenes[s], &q)) || (rc = check_walkable(q, 0)) || (rc = scene_tree_height(q, d->scenes[s], &h)) ||
+            (rc = check_walkable(q, h)))
+            return rc;
+        *height = h > *height ? h : *height;
+    }
+    return SHRAY_OK;
+}
+
+template <int SLOTS>
+void launch_form(dim3 grid, size_t lds, hipStream_t stream, const ShrayInstanceSetDevice &d, const SetWork &w)
+{
+    const TopNode *nodes = static_cast<const TopNode *>(d.nodes);
+    const float4 *records = static_cast<const float4 *>(d.records);
+    const SceneView *views = static_cast<const SceneView *>(d.views);
+    if (w.counters)
+        hipLaunchKernelGGL((instance_all_hits_kernel<SLOTS, false, true>), grid, dim3(kBlock), lds, stream, w, nodes, records, views);
+    else if (w.counts || w.k == 0)
+        hipLaunchKernelGGL((instance_all_hits_kernel<SLOTS, false, false>), grid, dim3(kBlock), lds, stream, w, nodes, records, views);
+    else
+        hipLaunchKernelGGL((instance_all_hits_kernel<SLOTS, true, false>), grid, dim3(kBlock), lds, stream, w, nodes, records, views);
+}
+
+int trace_device(shray_instance_set *set, const shray_multihit_params *mp, const shray_ray *d_rays, int64_t count, shray_hit *d_hits,
+                 int32_t *d_instances, int32_t *d_counts, hipStream_t stream, DeviceCounters *d_counters)
+{
+    int rc = check_query(set, mp, d_rays, count, d_hits, d_counts);
+    if (rc)
+        return rc;
+    const int k = mp->max_hits;
+    if (!aligned(d_rays, 16) || (k > 0 && !aligned(d_hits, 16)) || !aligned(d_instances, 4) || !aligned(d_counts, 4))
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "ray and hit buffers must be 16-byte aligned, the instances and counts 4-byte aligned");
+    if (count == 0)
+        return SHRAY_OK;
+    ShrayInstanceSetDevice d;
+    int height = 0;
+    if ((rc = enter_set(set, &d, &height)))
+        return rc;
+    // the form that keeps its K best in the ray's output slots keeps the instance half of the keys there too: without an
+    // instance buffer of the caller's, in scratch that is taken and given back in stream order
+    const bool in_memory = k > 8;
+    int32_t *scratch = nullptr;
+    if (in_memory && !d_instances) {
+        HIP_TRY(hipMallocAsync((void **)&scratch, (size_t)count * (size_t)k * sizeof(int32_t), stream));
+        d_instances = scratch;
+    }
+    const int levels = height > 0 ? height : 1;
+    SetWork w{(const float4 *)d_rays, k > 0 ? (float4 *)d_hits : nullptr, k > 0 ? d_instances : nullptr, d_counts, (uint64_t)count, 0, k,
+              mp->max_leaf_tests, levels, d_counters};
+    const size_t lds = ((size_t)kBlock * (size_t)levels + kTopStack) * sizeof(uint32_t);
+    rc = for_each_launch(((uint64_t)count + kBlock - 1) / kBlock, kRaysPerLaunch / kBlock, [&](uint64_t first, dim3 grid) {
+        w.first = first * kBlock;
+        if (k == 0 || in_memory)
+            launch_form<kSlotsInMemory>(grid, lds, stream, d, w);
+        else if (k == 1)
+            launch_form<1>(grid, lds, stream, d, w);
+        else if (k == 2)
+            launch_form<2>(grid, lds, stream, d, w);
+        else if (k <= 4)
+            launch_form<4>(grid, lds, stream, d, w);
+        else
+            launch_form<8>(grid, lds, stream, d, w);
+        return launched("instanced all-hits ray query");
+    });
+    if (scratch) {
+        const hipError_t e = hipFreeAsync(scratch, stream);
+        if (e != hipSuccess && !rc)
+            rc = fail(SHRAY_ERR_DEVICE, "hipFreeAsync failed: %s", hipGetErrorString(e));
+    }
+    return rc;
+}
+
+// the blocking forms: the rays to the device, the query on the null stream, the records, instances, counts (and tallies) back
+int trace_host(shray_instance_set *set, const shray_multihit_params *mp, const shray_ray *rays, int64_t count, shray_hit *hits,
+               int32_t *instances, int32_t *counts, shray_counters *out)
+{
+    int rc = check_query(set, mp, rays, count, hits, counts);
+    if (rc)
+        return rc;
+    if (out) {
+        memset(out, 0, sizeof(*out));
+        out->samples = (uint64_t)count;
+    }
+    if (count == 0)
+        return SHRAY_OK;
+    ShrayInstanceSetDevice d;
+    int height = 0;
+    if ((rc = enter_set(set, &d, &height)))   // (the errors of a set come before any allocation)
+        return rc;
+    const size_t n = (size_t)count, k = (size_t)mp->max_hits;
+    return run_blocking({{rays, n * sizeof(shray_ray)}},
+                        {{hits, n * k * sizeof(shray_hit)}, {instances, instances ? n * k * sizeof(int32_t) : 0}, {counts, counts ? n * sizeof(int32_t) : 0}},
+                        out, [&](DeviceBuffer *d_rays, DeviceBuffer *d_out, DeviceCounters *shards) {
+                            return trace_device(set, mp, d_rays->as<const shray_ray>(), count, d_out[0].as<shray_hit>(),
+                                                d_out[1].as<int32_t>(), d_out[2].as<int32_t>(), nullptr, shards);
+                        });
+}
+
+}   // namespace
+
+static_assert(sizeof(shray_multihit_params) == 16, "shray_multihit_params is 16 bytes");
+static_assert(sizeof(shray_ray) == 32 && sizeof(shray_hit) == 16, "the ray query's records");
+
+extern "C" {
+
+int shray_trace_instances_all_hits_device(shray_instance_set *set, const shray_multihit_params *mp, const shray_ray *d_rays,
+                                          int64_t count, shray_hit *d_hits, int32_t *d_instances, int32_t *d_counts, void *hip_stream)
+{
+    return trace_device(set, mp, d_rays, count, d_hits, d_instances, d_counts, (hipStream_t)hip_stream, nullptr);
+}
+
+int shray_trace_instances_all_hits(shray_instance_set *set, const shray_multihit_params *mp, const shray_ray *rays, int64_t count,
+                                   shray_hit *hits, int32_t *instances, int32_t *counts)
+{
+    return trace_host(set, mp, rays, count, hits, instances, counts, nullptr);
+}
+
+int shray_trace_instances_all_hits_counters(shray_instance_set *set, const shray_multihit_params *mp, const shray_ray *rays,
+                                            int64_t count, shray_hit *hits, int32_t *instances, int32_t *counts, shray_counters *out)
+{
+    if (!out)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "counters is NULL");
+    return trace_host(set, mp, rays, count, hits, instances, counts, out);
+}
+
+}   // extern "C"

@@ -980,6 +980,70 @@ class InstanceSet:
         N.check(self._lib.shray_trace_instances_device(self._handle, C.byref(qp), C.c_void_p(rays_ptr), count, C.c_void_p(hits_ptr),
                                                        C.c_void_p(instances_ptr or None), C.c_void_p(stream_ptr)))
 
+    def trace_all_hits(self, rays, max_hits: int = 8, counts: bool = True, max_leaf_tests: int = 10, counters: bool = False):
+        """Instanced all-hits ray queries (include/shader_ray_instance_multihit.h): per world ray the number of surfaces it
+        crosses over all instances and its first `max_hits` crossings, sorted by (t, instance, triangle), the other slots
+        {tmax, 0, 0, HIT_MISS} with instance -1.  `rays` as for Scene.trace_all_hits: host rays take the blocking path and
+        return (hits: HIT_DTYPE [n, max_hits], instances: int32 [n, max_hits], counts: int32 [n]); a float32 [n, 8] GPU tensor
+        on the set's device takes the device path on the current torch stream and returns (int32 [n, max_hits, 4] tensor of
+        shray_hit records, int32 [n, max_hits] tensor, int32 [n] tensor).  counts=False returns None for the counts and lets
+        the walks skip what cannot reach the first `max_hits` (the same records); max_hits = 0 returns None for the hits and
+        instances.  counters=True (host rays only) also returns the counters of the form that skips nothing, summed over
+        a ray's walks."""
+        lib = N.load_instance_multihit()
+        mp = multihit_params(max_hits, max_leaf_tests)
+        if max_hits == 0 and not counts:
+            raise ValueError("nothing is asked for: max_hits is 0 and counts is False")
+        rays = _host_if_cpu(rays)
+        if _is_torch(rays):
+            import torch
+            if counters:
+                raise ValueError("counters are counted on the host path: pass host rays")
+            if rays.device.index != self.device:
+                raise ValueError(f"rays are on {rays.device}, the set on cuda:{self.device}")
+            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+                raise ValueError("a GPU ray tensor must be float32 [n, 8] (the shray_ray layout)")
+            r = rays.contiguous()
+            hits = torch.empty((len(r), max_hits, 4), dtype=torch.int32, device=r.device) if max_hits > 0 else None
+            inst = torch.empty((len(r), max_hits), dtype=torch.int32, device=r.device) if max_hits > 0 else None
+            cnt = torch.empty(len(r), dtype=torch.int32, device=r.device) if counts else None
+            stream = torch.cuda.current_stream(r.device)
+            r.record_stream(stream)   # (the query reads it after this call returns)
+            N.check(lib.shray_trace_instances_all_hits_device(
+                self._handle, C.byref(mp), C.c_void_p(r.data_ptr()), len(r), C.c_void_p(hits.data_ptr() if hits is not None else None),
+                C.c_void_p(inst.data_ptr() if inst is not None else None), C.c_void_p(cnt.data_ptr() if counts else None),
+                C.c_void_p(stream.cuda_stream)))
+            return hits, inst, cnt
+        rays = _host_rays(rays)
+        hits = np.empty((len(rays), max_hits), HIT_DTYPE) if max_hits > 0 else None   # (the library refuses a negative one)
+        inst = np.empty((len(rays), max_hits), np.int32) if max_hits > 0 else None
+        cnt = np.empty(len(rays), np.int32) if counts else None
+        args = (self._handle, C.byref(mp), rays.ctypes.data_as(C.c_void_p), len(rays),
+                hits.ctypes.data_as(C.c_void_p) if hits is not None else None,
+                inst.ctypes.data_as(C.c_void_p) if inst is not None else None, cnt.ctypes.data_as(C.c_void_p) if counts else None)
+        if counters:
+            c = N.Counters()
+            N.check(lib.shray_trace_instances_all_hits_counters(*args, C.byref(c)))
+            return hits, inst, cnt, c.as_dict()
+        N.check(lib.shray_trace_instances_all_hits(*args))
+        return hits, inst, cnt
+
+    def trace_all_hits_into(self, rays_ptr: int, count: int, hits_ptr: int, instances_ptr: int = 0, counts_ptr: int = 0,
+                            max_hits: int = 8, stream_ptr: int = 0, max_leaf_tests: int = 10):
+        """Asynchronous instanced all-hits queries on device memory of the set's device
+        (shray_trace_instances_all_hits_device): `count` shray_ray records at `rays_ptr` -> count * max_hits shray_hit records
+        at `hits_ptr` (0 iff max_hits is 0), unless `instances_ptr` is 0 count * max_hits int32 instance indices there, and
+        unless `counts_ptr` is 0 `count` int32 crossing counts there, on a HIP stream (`stream_ptr`)."""
+        mp = multihit_params(max_hits, max_leaf_tests)
+        N.check(N.load_instance_multihit().shray_trace_instances_all_hits_device(
+            self._handle, C.byref(mp), C.c_void_p(rays_ptr), count, C.c_void_p(hits_ptr or None), C.c_void_p(instances_ptr or None),
+            C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+
+    def crossing_counts(self, rays, max_leaf_tests: int = 10):
+        """How many surfaces each world ray crosses before its tmax over all instances (trace_all_hits with max_hits = 0):
+        int32 [n], numpy for host rays, a tensor for GPU rays."""
+        return self.trace_all_hits(rays, max_hits=0, counts=True, max_leaf_tests=max_leaf_tests)[2]
+
     def close(self):
         if getattr(self, "_handle", None):
             self._lib.shray_instance_set_destroy(self._handle)
