@@ -34,6 +34,12 @@
  * it is above the K-th smallest dist2 held, which starts at max_dist2 (a node whose bound equals it is visited: a lower
  * triangle index wins a tie).  Every triangle of a visited leaf is tested.
  *
+ * Coordinate range.  As the closest-point query's (include/shader_ray_point.h), over every pair within the radius: measured
+ * on meshes whose largest coordinate is 1.7 scaled by S = 2^k (tests/point_scale_cases.py), the counts
+ * and all K = 64 records are the exact images of the unscaled ones for -24 <= k <= 28.  Outside, the contract above holds bit
+ * for bit with that header's invariants per record, the records sorted by (dist2, index) and n the number of triangles with
+ * dist2 <= max_dist2; where every dist2 underflows to 0 or overflows to +inf the order is the index order.
+ *
  * Errors: count == 0 is a no-op.  A wrong struct_size, K outside [0, SHRAY_NEAR_MAX], a nonzero reserved field, a negative
  * count, a NULL scene, params or point pointer, a NULL record pointer with K > 0, K == 0 together with no counts (nothing is
  * asked for; with K == 0 the record pointer is neither read nor written), a point or record pointer that is not 16-byte

@@ -40,6 +40,17 @@
  *   - The first query of a scene reads the tree's topology back once, synchronously, to size the stack; the height is then
  *     kept with the scene (a refit does not change it).
  *
+ * Coordinate range.  va, vb and vc are of degree 4 in the coordinates, so they leave fp32's normal range long before the
+ * positions do.  Measured with the brute-force definition on meshes whose largest coordinate is 1.7, with positions, points
+ * and radii scaled by S = 2^k (tests/point_scale_cases.py): every record is the exact image of the
+ * unscaled one (q * S, dist2 * S^2, the same u, v, triangle and region, bit for bit) for -25 <= k <= 32.  Outside that range
+ * the definition above still holds bit for bit, subnormals, infinities and NaNs included (no flush to zero, no approximate
+ * division), and so do its invariants: triangle is in range or SHRAY_HIT_MISS, region in -1 .. 6, q lies in the reported
+ * triangle's vertex box, dist2 = dot(p-q, p-q) recomputed and never NaN (a NaN q is replaced by the clamp's selects), the
+ * lowest index wins a tie (when every dist2 underflows to 0 or overflows to +inf that is triangle 0, and the walk skips
+ * nothing: 0 > 0 and inf > inf are false).  But the record no longer names the geometrically nearest triangle: a third to a
+ * half of the points get another one.
+ *
  * Errors: count == 0 is a no-op.  A negative count, a NULL pointer or a device pointer that is not 16-byte aligned fail
  * with SHRAY_ERR_INVALID_ARGUMENT.  Counts beyond one launch's grid are split over launches.  A query enqueued on a stream
  * after a refit on that stream sees the refit geometry.

@@ -40,6 +40,14 @@
  *     traverse it (a -> b, b -> c, c -> a) from the same welded vertex.  closed = no boundary, non-manifold or misoriented
  *     edge.  A degenerate triangle is one whose nhat is 0.
  *
+ * Coordinate range.  The closest part has the point query's range (include/shader_ray_point.h).  dot(n, n) is of degree 4
+ * under sqrtf, the pseudonormals are of degree 0.  Measured on meshes whose largest coordinate is 1.7 scaled by S = 2^k
+ * (tests/point_scale_cases.py): the sign data is bit-identical to the unscaled scene's for
+ * -26 <= k <= 33, and the signed values are the unscaled ones times S for -26 <= k <= 32.  Outside, the rules above are
+ * applied as written: as dot(n, n) underflows to 0 or overflows to +inf, triangles count as degenerate (all of them from
+ * k = -36 down and from k = 37 up) and their nhat is 0; the welded topology does not depend on the scale; the value is NaN
+ * exactly on a miss and its magnitude is sqrtf(dist2); its sign means nothing.
+ *
  * What is derived, and when.  The pseudonormals are derived on the device, per scene, by the first signed query (or
  * surface_info / sign_data download) and kept with the scene; the derivation is enqueued on that call's stream and needs
  * no readback.  An event recorded after it orders it for everything else: a later query on another stream waits for it on

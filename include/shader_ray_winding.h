@@ -42,6 +42,15 @@
  *   - Winding-signed distance: the closest-point query (shray_closest_points's record, bit for bit) with the sign from w:
  *     -sqrtf(dist2) if w > 0.5 and dist2 > 0, else +sqrtf(dist2); NaN on a miss (w is then not computed).
  *
+ * Coordinate range.  det and den are of degree 3 in the coordinates, T_far's dot(d, m) of degree 5.  Measured on meshes whose
+ * largest coordinate is 1.7 scaled by S = 2^k (tests/point_scale_cases.py): in the exact mode w is
+ * bit-identical to the unscaled scene's for -33 <= k <= 31.  A finite beta is not covariant (node boxes carry an absolute
+ * 1e-5 pad, which moves r): its inside test w > 0.5 agrees with the exact mode's away from the surface for -31 <= k <= 20.
+ * Outside, the rules above are applied as written: w = +0 for every finite point once every det underflows (k <= -57); w is
+ * NaN for a finite point whenever a term is, which in the exact mode is det = inf - inf (no point up to k = 36, every point
+ * from k = 44) and for a finite beta already dot(d, m) = inf - inf (the far points from k = 21, every point for
+ * 28 <= k <= 34); from k = 35 up A is +inf, no node is far, and a finite beta gives the exact mode's bits.
+ *
  * What is derived, and when.  The node records are derived on the device, per scene, by the first query (or download) and
  * kept with the scene; the derivation is enqueued on that call's stream.  That first call also reads the tree's topology
  * back once, synchronously (a refit never changes it).  An event recorded after each derivation orders it for everything
