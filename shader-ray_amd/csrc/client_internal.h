@@ -1,6 +1,8 @@
 // client_internal.h -- the host-side scaffolding that the client libraries of libshray_hip.so (query/, refit/, instance/,
-// point/) share: an owning device allocation, the device switch, the launch check, the split of a large launch and the blocking
-// form of a query.  Host-only, internal to the libraries; not part of the C ABI.
+// point/, sdf/, winding/, multihit/, near/, instance_multihit/) share: an owning device allocation, the device switch, the
+// launch check and the grid of a launch, the split of a large launch, the blocking form of a query, the upload of a tree's
+// height order (tree_order.h) and the bookkeeping of what a library derives from a scene's geometry (DerivedState).
+// Host-only, internal to the libraries; not part of the C ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,6 +14,7 @@
 #include "device_types.h"
 #include "error_internal.h"
 #include "scene_access_internal.h"
+#include "tree_order.h"
 
 namespace {
 
@@ -73,6 +76,9 @@ inline int launched(const char *what)
     return e == hipSuccess ? SHRAY_OK : fail(SHRAY_ERR_DEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
 }
 
+// workgroups of `block` threads for `items` threads
+inline unsigned int grid_of(uint64_t items, int block) { return (unsigned int)((items + block - 1) / block); }
+
 // `blocks` workgroups in launches of at most `per_launch`: launch(first block, grid) for each, up to the first error
 template <typename Launch>
 int for_each_launch(uint64_t blocks, uint64_t per_launch, Launch &&launch)
@@ -121,6 +127,66 @@ int run_blocking(const HostIn (&in)[NI], const HostOut (&out)[NO], shray_counter
         if (out[k].host && out[k].bytes)
             HIP_TRY(hipMemcpy(out[k].host, d_out[k].p, out[k].bytes, hipMemcpyDeviceToHost));
     return counters ? sum_counter_shards(shards.as<const shray::DeviceCounters>(), counters) : SHRAY_OK;
+}
+
+// A TreeOrder on the device, as the bottom-up kernels read it: `order`, `topo` (per node) and `heights` (height_start).
+struct DeviceTreeOrder {
+    DeviceBuffer order, topo, heights;
+};
+
+// `t`'s arrays onto the device and released on the host: by blocking copies, or by copies enqueued on `stream` and one
+// synchronisation of it
+inline int upload_tree_order(TreeOrder &t, DeviceTreeOrder &d, bool blocking, hipStream_t stream)
+{
+    const auto put = [&](DeviceBuffer &to, const void *from, size_t bytes) {
+        HIP_TRY(to.alloc(bytes));
+        HIP_TRY(blocking ? hipMemcpy(to.p, from, bytes, hipMemcpyHostToDevice) : hipMemcpyAsync(to.p, from, bytes, hipMemcpyHostToDevice, stream));
+        return (int)SHRAY_OK;
+    };
+    int rc = put(d.order, t.order.data(), t.order.size() * sizeof(uint32_t));
+    rc = rc ? rc : put(d.topo, t.topo.data(), t.topo.size() * sizeof(Topo));
+    rc = rc ? rc : put(d.heights, t.height_start.data(), t.height_start.size() * sizeof(uint32_t));
+    if (!rc && !blocking)
+        HIP_TRY(hipStreamSynchronize(stream));
+    std::vector<uint32_t>().swap(t.order);   // (the schedule needs height_start and the counts only)
+    std::vector<Topo>().swap(t.topo);
+    return rc;
+}
+
+// What a library derives on the device from a scene's geometry (the signed distance's sign data, the winding number's node
+// records) is current when `derived` is set and `generation` is the scene's geometry generation (scene_access_internal.h: a
+// refit bumps it).  `done` is recorded after every derivation: other streams and the blocking calls wait on it.
+struct DerivedState {
+    bool derived = false;
+    uint64_t generation = 0;
+    hipEvent_t done = nullptr;
+    DerivedState() { (void)hipEventCreateWithFlags(&done, hipEventDisableTiming); }   // (make_current reports a failure)
+    ~DerivedState()
+    {
+        if (done)
+            (void)hipEventDestroy(done);
+    }
+};
+
+// What `st` derives made current on `stream`: when it is stale, derive() enqueued there and the event recorded after it;
+// else `stream` waits for the event of the derivation, which may have run on another stream (no host synchronisation
+// either way).  A derivation that fails leaves the state stale.
+template <typename Derive>
+int make_current(DerivedState &st, uint64_t generation, hipStream_t stream, Derive &&derive)
+{
+    if (!st.done)
+        return fail(SHRAY_ERR_DEVICE, "the event that orders a scene's derived data could not be created");
+    if (st.derived && st.generation == generation) {
+        HIP_TRY(hipStreamWaitEvent(stream, st.done, 0));
+        return SHRAY_OK;
+    }
+    st.derived = false;
+    if (const int rc = derive())
+        return rc;
+    HIP_TRY(hipEventRecord(st.done, stream));
+    st.derived = true;
+    st.generation = generation;
+    return SHRAY_OK;
 }
 
 }   // namespace

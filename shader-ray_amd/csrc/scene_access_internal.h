@@ -36,7 +36,7 @@ struct ShrayRefitScene {
     uint32_t exact_div_ok;
     bool packed_ok;
     int device;
-    std::shared_ptr<void> *state;      // the refit library's own per-scene data (level order, scratch); destroyed with the scene
+    std::shared_ptr<void> *state;      // the refit library's own per-scene data (tree_order.h's height order, scratch); destroyed with the scene
 };
 
 extern "C" int shrayi_scene_refit_view(shray_scene *scene, ShrayRefitScene *out);
@@ -47,10 +47,11 @@ extern "C" int shrayi_scene_set_exact_div_ok(shray_scene *scene, uint32_t ok);
 extern "C" int shrayi_scene_point_state(shray_scene *scene, std::shared_ptr<void> **out);
 
 // libshray_sdf.so's own per-scene data (include/shader_ray_sdf.h: the sign data), destroyed with the scene, and the scene's
-// geometry generation: a host-side count of the refits that wrote new positions.  Host-only, no device work.
+// geometry generation: a host-side count of the refits that wrote new positions, which client_internal.h's make_current
+// compares with the one the data was derived at.  Host-only, no device work.
 extern "C" int shrayi_scene_sdf_state(shray_scene *scene, std::shared_ptr<void> **out, uint64_t *generation);
-// libshray_winding.so's own per-scene data (include/shader_ray_winding.h: the node records), destroyed with the scene, and the
-// same geometry generation.  Host-only, no device work.
+// libshray_winding.so's own per-scene data (include/shader_ray_winding.h: the node records and tree_order.h's height order),
+// destroyed with the scene, and the same geometry generation.  Host-only, no device work.
 extern "C" int shrayi_scene_winding_state(shray_scene *scene, std::shared_ptr<void> **out, uint64_t *generation);
 // called by a refit (host or device form) once its validation has passed, before it enqueues the writes of new positions
 extern "C" int shrayi_scene_geometry_changed(shray_scene *scene);

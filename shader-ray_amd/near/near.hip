@@ -33,7 +33,6 @@ using namespace shray;
 
 namespace {
 
-constexpr uint64_t kPointsPerLaunch = 1ull << 24;   // the grid's threads stay far below 2^32
 constexpr int kSlotsInMemory = 0;   // SLOTS of the instance that keeps its K best in the point's output slots
 #if SHRAY_NEAR_NAME_STACK
 using StackEntry = uint32_t;
@@ -56,14 +55,6 @@ struct NearWork {
 __device__ __forceinline__ bool before(float d, int tri, float slot_d, int slot_tri)
 {
     return slot_tri < 0 || d < slot_d || (d == slot_d && tri < slot_tri);
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long x)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        x += __shfl_xor(x, off);
-    return x;
 }
 
 // One lane per point.  SLOTS: the register slots of the K best keys (k <= SLOTS), kSlotsInMemory: the records live in the

@@ -1,12 +1,14 @@
 // packed_walk.h -- what the one-lane-per-item walks over octant copy 7 of the packed tree share (the closest-point walk,
-// point_walk.h, and the all-hits ray walk, multihit/multihit.hip): a record's load, the tree's height and where it is kept per
-// scene, and the refusals of a scene before anything is launched.  Internal to the libraries; no kernel is defined here.
+// point_walk.h, the within-radius walk, near/near.hip, the winding-number walk, winding/winding.hip, and the all-hits ray
+// walk, multihit/multihit.hip): a record's load, the sum over a wave that flushes a walk's work counters, the points of one launch, the readback
+// of copy 7 into csrc/tree_order.h's height order, the tree's height and where it is kept per scene, and the refusals of a
+// scene before anything is launched.  Internal to the libraries; no kernel is defined here.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <memory>
-#include <utility>
+#include <string>
 #include <vector>
 
 #include "client_internal.h"
@@ -15,6 +17,7 @@
 #include "packed_layout.h"
 #include "scene_access_internal.h"
 #include "shader_ray_point.h"
+#include "tree_order.h"
 
 namespace {
 
@@ -22,6 +25,7 @@ using namespace shray;
 
 constexpr int kBlock = 64;    // one wave per workgroup: a lane's stack column is its own
 constexpr int kOctant = 7;    // the copy whose entry planes are boxmin and exit planes boxmax
+constexpr uint64_t kPointsPerLaunch = 1ull << 24;   // the grid's threads stay far below 2^32
 
 struct Box {
     float lo[3], hi[3];
@@ -49,38 +53,35 @@ __device__ __forceinline__ Record load_record(const char *copy, uint32_t name)
     return r;
 }
 
-// Edges from the root to the deepest leaf of the packed tree: a function of the topology only, which a refit does not change.
-// A blocking readback of the tree; the libraries keep the result per scene.
-inline int packed_tree_height(const ShrayQueryScene &q, int *height)
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long x)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        x += __shfl_xor(x, off);
+    return x;
+}
+
+// The packed tree's topology in height order (tree_order.h), for bottom-up launches whose one workgroup takes the heights
+// of at most `tail_width` nodes: a function of the topology only, which a refit does not change.  A blocking readback of
+// copy 7; the libraries keep what they need of the result per scene.
+inline int packed_tree_order(const ShrayQueryScene &q, uint32_t tail_width, TreeOrder *out)
 {
     const uint32_t nodes = q.view.packed_nodes_bytes / (uint32_t)sizeof(DeviceNode);
     std::vector<DeviceNode> host(nodes);
     const char *copy = static_cast<const char *>(q.view.packed_nodes) + (size_t)kOctant * q.view.packed_nodes_bytes;
     HIP_TRY(hipMemcpy(host.data(), copy, q.view.packed_nodes_bytes, hipMemcpyDeviceToHost));
-    // depth-first from the root; a node's name is its byte offset / 8, so its index is name / 4
-    const uint32_t per = (uint32_t)(sizeof(DeviceNode) >> kNodeNameShift);
-    std::vector<std::pair<uint32_t, int>> todo{{q.view.packed_root, 0}};
-    int deepest = 0;
-    uint64_t seen = 0;
-    while (!todo.empty()) {
-        const auto [name, depth] = todo.back();
-        todo.pop_back();
-        if (name % per || name / per >= nodes || ++seen > nodes)
-            return fail(SHRAY_ERR_BAD_TREE, "the packed tree names node %u of %u (or visits a node twice)", name / per, nodes);
-        const DeviceNode &n = host[name / per];
-        if (n.b & kLeafFlag) {
-            const uint64_t end = (uint64_t)n.a + (n.b & ~kLeafFlag);
-            if (end > q.view.triangle_count)
-                return fail(SHRAY_ERR_BAD_TREE, "a leaf of the packed tree names triangles up to %llu of %u", (unsigned long long)end,
-                            q.view.triangle_count);
-            deepest = depth > deepest ? depth : deepest;
-        } else {
-            todo.push_back({n.a & kChildNameMask, depth + 1});
-            todo.push_back({n.b, depth + 1});
-        }
-    }
-    *height = deepest;
-    return SHRAY_OK;
+    const std::string refused = tree_order(host.data(), nodes, q.view.packed_root, q.view.triangle_count, kOctant, tail_width, out);
+    return refused.empty() ? SHRAY_OK : fail(SHRAY_ERR_BAD_TREE, "%s", refused.c_str());
+}
+
+// edges from the root to the deepest leaf of the packed tree
+inline int packed_tree_height(const ShrayQueryScene &q, int *height)
+{
+    TreeOrder t;
+    const int rc = packed_tree_order(q, UINT32_MAX, &t);
+    if (!rc)
+        *height = t.height;
+    return rc;
 }
 
 // the walk's refusals of a scene before anything is launched: no packed tree, or one deeper than the LDS stack holds

@@ -26,9 +26,6 @@ namespace {
 
 using namespace shray;
 
-
-constexpr uint64_t kPointsPerLaunch = 1ull << 24;   // the grid's threads stay far below 2^32
-
 // the stack of one workgroup: (node name, box bound) per level, level-major so that a wave's accesses are consecutive
 inline size_t stack_bytes(int height) { return (size_t)kBlock * (size_t)(height > 0 ? height : 1) * sizeof(uint2); }
 
@@ -39,14 +36,6 @@ struct PointWork {
     uint64_t first;         // this launch's first point
     DeviceCounters *counters;
 };
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long x)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        x += __shfl_xor(x, off);
-    return x;
-}
 
 // One lane per point.  COUNT: the counting instance (node_visits, leaf_visits, triangle_tests into kCounterShards shards).
 template <bool COUNT>

@@ -7,7 +7,8 @@
 // words are not touched.  Boxes are built bottom-up by node HEIGHT (a leaf 0, a branch one above its higher child): a node
 // of height h reads only boxes of lower heights, and fewer nodes have height h than h - 1 (every one of them has a child of
 // height h - 1 of its own), so the wide heights get a launch each -- the launch boundary is the hand-off between workgroups --
-// and the narrow rest one workgroup that steps through them behind barriers.  This library is built apart from
+// and the narrow rest one workgroup that steps through them behind barriers.  The heights, the order by height and that
+// schedule are csrc/tree_order.h's, from the first refit's one readback of octant copy 0.  This library is built apart from
 // libshray_hip.so, so the renderer's code objects do not change.
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,7 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "client_internal.h"
@@ -25,6 +27,7 @@
 #include "packed_layout.h"
 #include "scene_access_internal.h"
 #include "shader_ray_refit.h"
+#include "tree_order.h"
 
 using namespace shray;
 
@@ -106,11 +109,6 @@ __global__ void rf_corners(uint32_t nt, const float *__restrict__ vertex_data, i
     }
     tris[t] = pt;
 }
-
-// topology of a packed node: a leaf {first triangle, count | kLeafFlag}, a branch {negative child, positive child}
-struct Topo {
-    uint32_t x, y;
-};
 
 // one thread per leaf: box3d().add(v - bumpout, v + bumpout) over the corners of its triangles (an empty range keeps the
 // initial box, +-FLT_MAX)
@@ -262,88 +260,29 @@ __global__ void __launch_bounds__(kBlock) rf_finish(uint32_t blocks, const doubl
     }
 }
 
-// What the refit keeps per scene (the scene owns it: ShrayRefitScene::state): the nodes ordered by height, their topology
-// and the scratch of the passes.  Built by the first refit from the packed tree's child words, which a refit never changes.
+// What the refit keeps per scene (the scene owns it: ShrayRefitScene::state): the nodes ordered by height and their topology
+// on the device, the schedule over the heights, and the scratch of the passes.  Built by the first refit from the packed
+// tree's child words, which a refit never changes.
 struct RefitState {
-    uint32_t n = 0, nt = 0, leaves = 0;
-    std::vector<uint32_t> height_start;   // order[height_start[h] .. height_start[h + 1]) have height h; h = 0: the leaves
-    uint32_t tail_height = 0;             // first height of the one-workgroup launch
-    DeviceBuffer order, topo, heights, boxes, partial, facts, staging;
+    TreeOrder levels;         // (its per-node arrays are released once they are on the device)
+    DeviceTreeOrder tree;
+    DeviceBuffer boxes, partial, facts, staging;
 };
 
+// the one readback (octant copy 0), its order by height onto the device, and the scratch
 int build_state(const ShrayRefitScene &v, hipStream_t stream, RefitState &st)
 {
     const uint32_t n = v.node_count, nt = v.triangle_count;
     std::vector<DeviceNode> copy0(n);
     HIP_TRY(hipMemcpyAsync(copy0.data(), v.packed_nodes, (size_t)n * sizeof(DeviceNode), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    // octant 0 (no axis bit set) visits the positive child first: a' = axis bit | positive name, b' = negative name
-    std::vector<Topo> topo(n);
-    for (uint32_t k = 0; k < n; k++) {
-        const DeviceNode &d = copy0[k];
-        if (d.b & kLeafFlag) {
-            if ((uint64_t)d.a + (d.b & ~kLeafFlag) > nt)
-                return fail(SHRAY_ERR_BAD_TREE, "packed leaf %u names triangles beyond the scene's %u", k, nt);
-            topo[k] = {d.a, d.b};
-        } else {
-            const uint32_t pos = (d.a & kChildNameMask) >> (kNodeShift - kNodeNameShift), neg = d.b >> (kNodeShift - kNodeNameShift);
-            if (pos >= n || neg >= n)
-                return fail(SHRAY_ERR_BAD_TREE, "packed node %u names a child beyond the tree's %u nodes", k, n);
-            topo[k] = {neg, pos};
-        }
-    }
-    // heights, by a post-order walk from the root (which also proves every node is reached once)
-    std::vector<uint32_t> height(n, 0);
-    std::vector<uint8_t> seen(n, 0);
-    std::vector<std::pair<uint32_t, bool>> todo{{v.packed_root, false}};
-    uint32_t reached = 0, tallest = 0;
-    while (!todo.empty()) {
-        const auto [k, expanded] = todo.back();
-        todo.pop_back();
-        const bool leaf = topo[k].y & kLeafFlag;
-        if (!expanded) {
-            if (seen[k]++)
-                return fail(SHRAY_ERR_BAD_TREE, "packed node %u is reached twice", k);
-            reached++;
-            if (!leaf) {
-                todo.push_back({k, true});
-                todo.push_back({topo[k].x, false});
-                todo.push_back({topo[k].y, false});
-            }
-        } else {
-            height[k] = 1 + std::max(height[topo[k].x], height[topo[k].y]);
-            tallest = std::max(tallest, height[k]);
-        }
-    }
-    if (reached != n)
-        return fail(SHRAY_ERR_BAD_TREE, "the packed tree reaches %u of its %u nodes", reached, n);
-    // counting sort by height
-    st.height_start.assign(tallest + 2, 0);
-    for (uint32_t k = 0; k < n; k++)
-        st.height_start[height[k] + 1]++;
-    for (uint32_t h = 0; h <= tallest; h++)
-        st.height_start[h + 1] += st.height_start[h];
-    std::vector<uint32_t> order(n), next(st.height_start.begin(), st.height_start.end() - 1);
-    for (uint32_t k = 0; k < n; k++)
-        order[next[height[k]]++] = k;
-    st.n = n;
-    st.nt = nt;
-    st.leaves = st.height_start[1];
-    st.tail_height = 1;
-    while (st.tail_height <= tallest && st.height_start[st.tail_height + 1] - st.height_start[st.tail_height] > (uint32_t)kTailBlock)
-        st.tail_height++;
-    const uint32_t emit_blocks = (n + kBlock - 1) / kBlock;
-    HIP_TRY(st.order.grow((size_t)n * sizeof(uint32_t)));
-    HIP_TRY(st.topo.grow((size_t)n * sizeof(Topo)));
-    HIP_TRY(st.heights.grow(st.height_start.size() * sizeof(uint32_t)));
+    const std::string refused = tree_order(copy0.data(), n, v.packed_root << (kNodeShift - kNodeNameShift), nt, 0, kTailBlock, &st.levels);
+    if (!refused.empty())
+        return fail(SHRAY_ERR_BAD_TREE, "%s", refused.c_str());
     HIP_TRY(st.boxes.grow((size_t)n * sizeof(Box)));
-    HIP_TRY(st.partial.grow((size_t)emit_blocks * sizeof(double)));
+    HIP_TRY(st.partial.grow((size_t)grid_of(n, kBlock) * sizeof(double)));
     HIP_TRY(st.facts.grow(sizeof(RefitFacts)));
-    HIP_TRY(hipMemcpyAsync(st.order.p, order.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(st.topo.p, topo.data(), (size_t)n * sizeof(Topo), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(st.heights.p, st.height_start.data(), st.height_start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));   // (the host vectors go out of scope)
-    return SHRAY_OK;
+    return upload_tree_order(st.levels, st.tree, false, stream);
 }
 
 int check_input(const shray_refit_input *in)
@@ -384,8 +323,6 @@ int scene_of(shray_scene *scene, const shray_refit_input *in, ShrayRefitScene *v
     return use_device(v->device);
 }
 
-unsigned int grid_of(uint64_t items, int block) { return (unsigned int)((items + block - 1) / block); }
-
 int refit_device(shray_scene *scene, const ShrayRefitScene &v, const shray_refit_input *in, shray_refit_stats *stats, hipStream_t stream)
 {
     std::shared_ptr<void> &slot = *v.state;
@@ -398,7 +335,7 @@ int refit_device(shray_scene *scene, const ShrayRefitScene &v, const shray_refit
     }
     RefitState &st = *static_cast<RefitState *>(slot.get());
     RefitFacts *d_facts = (RefitFacts *)st.facts.p;
-    const uint32_t n = st.n, nt = st.nt;
+    const uint32_t n = v.node_count, nt = v.triangle_count;
     const uint64_t corners = 3ull * nt;
     const int stride = in->vertex_stride_floats, normal_offset = in->normal_offset_floats;
 
@@ -426,20 +363,25 @@ int refit_device(shray_scene *scene, const ShrayRefitScene &v, const shray_refit
         hipLaunchKernelGGL(rf_corners, dim3(grid_of(nt, kBlock)), dim3(kBlock), 0, stream, nt, in->vertex_data, stride, normal_offset,
                            in->triangle_vertices, v.positions, v.normals32, v.normals16, (PackedTri *)v.packed_tris);
     // 3. leaf boxes, 4. branch boxes by height
-    const uint32_t *order = (const uint32_t *)st.order.p;
-    const Topo *topo = (const Topo *)st.topo.p;
+    const uint32_t *order = st.tree.order.as<const uint32_t>();
+    const Topo *topo = st.tree.topo.as<const Topo>();
     Box *boxes = (Box *)st.boxes.p;
-    if (st.leaves)
-        hipLaunchKernelGGL(rf_leaves, dim3(grid_of(st.leaves, kBlock)), dim3(kBlock), 0, stream, st.leaves, order, topo,
-                           (const float *)v.positions, boxes);
-    const uint32_t heights = (uint32_t)st.height_start.size() - 1;
-    for (uint32_t h = 1; h < st.tail_height; h++) {
-        const uint32_t begin = st.height_start[h], count = st.height_start[h + 1] - begin;
-        hipLaunchKernelGGL(rf_branches, dim3(grid_of(count, kBlock)), dim3(kBlock), 0, stream, begin, count, order, topo, boxes);
-    }
-    if (st.tail_height < heights)
-        hipLaunchKernelGGL(rf_branches_tail, dim3(1), dim3(kTailBlock), 0, stream, (const uint32_t *)st.heights.p, st.tail_height,
-                           heights, order, topo, boxes);
+    for_each_level(
+        st.levels,
+        [&](uint32_t count) {
+            hipLaunchKernelGGL(rf_leaves, dim3(grid_of(count, kBlock)), dim3(kBlock), 0, stream, count, order, topo,
+                               (const float *)v.positions, boxes);
+            return SHRAY_OK;   // (one check after the last launch, below)
+        },
+        [&](uint32_t begin, uint32_t count) {
+            hipLaunchKernelGGL(rf_branches, dim3(grid_of(count, kBlock)), dim3(kBlock), 0, stream, begin, count, order, topo, boxes);
+            return SHRAY_OK;
+        },
+        [&](uint32_t first_height, uint32_t heights) {
+            hipLaunchKernelGGL(rf_branches_tail, dim3(1), dim3(kTailBlock), 0, stream, st.tree.heights.as<const uint32_t>(), first_height,
+                               heights, order, topo, boxes);
+            return SHRAY_OK;
+        });
     // 5. the boxes out, 6. the range check and the SAH cost
     const uint32_t emit_blocks = grid_of(n, kBlock);
     hipLaunchKernelGGL(rf_emit, dim3(emit_blocks), dim3(kBlock), 0, stream, n, (const Box *)boxes, topo, v.flat_of_packed, v.boxmin,

@@ -12,9 +12,10 @@
 //      nhat over its slots in ascending slot order and writes the sum to each slot; the topology counts come from the same
 //      lanes.
 // Every buffer is sized by the triangle count (3T corners, 3T slots), so nothing is read back; the derivation's buffers are
-// allocated and freed in stream order, and only the sign data and the counts stay with the scene.  An event recorded after
-// the derivation orders it for other streams and for the blocking calls.  This library is built apart from libshray_hip.so,
-// so the renderer's code objects do not change.
+// allocated and freed in stream order, and only the sign data and the counts stay with the scene.  When the sign data is
+// stale, and the event recorded after a derivation that orders it for other streams and for the blocking calls, are
+// csrc/client_internal.h's DerivedState.  This library is built apart from libshray_hip.so, so the renderer's code objects do
+// not change.
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -45,8 +46,6 @@ constexpr int kFaceAt = 0, kVertexAt = 3, kEdgeAt = 12;
 struct SurfaceCounts {
     unsigned long long vertices, edges, boundary, nonmanifold, misoriented, degenerate;
 };
-
-inline unsigned int grid_of(uint64_t n) { return (unsigned int)((n + kSdfBlock - 1) / kSdfBlock); }
 
 // the wave's flags added to one counter with one atomic (every lane of the wave calls it)
 __device__ __forceinline__ void count_wave(unsigned long long *counter, bool flag)
@@ -246,19 +245,11 @@ __global__ void __launch_bounds__(kSdfBlock) sd_sign(uint64_t count, const float
     out[i] = (s < 0.0f && r0.w > 0.0f) ? -d : d;
 }
 
-// What this library keeps per scene: the tree's height, the sign data and the surface counts, the geometry generation the
-// sign data was derived from, and an event recorded after the derivation (what other streams and the blocking calls wait on).
-struct SdfState {
+// What this library keeps per scene: the tree's height, the sign data and the surface counts, and when they were derived
+// (DerivedState).
+struct SdfState : DerivedState {
     int height = -1;                 // the packed tree's height, read once (a refit keeps the topology)
-    bool derived = false;
-    uint64_t generation = 0;
     DeviceBuffer sign, counts;
-    hipEvent_t done = nullptr;
-    ~SdfState()
-    {
-        if (done)
-            (void)hipEventDestroy(done);
-    }
 };
 
 int edge_bits(uint64_t corners)
@@ -269,12 +260,11 @@ int edge_bits(uint64_t corners)
     return bits;
 }
 
-// what a scene with nt triangles keeps: its sign data, the counts and the event
+// what a scene with nt triangles keeps: its sign data and the counts
 int allocate(SdfState &st, uint32_t nt)
 {
     HIP_TRY(st.sign.alloc((size_t)nt * SHRAY_SIGN_DATA_FLOATS * sizeof(float)));
     HIP_TRY(st.counts.alloc(sizeof(SurfaceCounts)));
-    HIP_TRY(hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
     return SHRAY_OK;
 }
 
@@ -321,32 +311,32 @@ int derive_into(const Scratch &sc, const SceneView &v, uint64_t n, float *sign, 
 {
     const uint32_t nt = v.triangle_count;
     size_t bytes = sc.temp_bytes;
-    hipLaunchKernelGGL(sd_triangles, dim3(grid_of(nt)), dim3(kSdfBlock), 0, stream, nt, v.positions, sign, sc.alpha, sc.zkey, sc.xykey,
+    hipLaunchKernelGGL(sd_triangles, dim3(grid_of(nt, kSdfBlock)), dim3(kSdfBlock), 0, stream, nt, v.positions, sign, sc.alpha, sc.zkey, sc.xykey,
                        sc.index, counts);
     if (const int rc = launched("signed-distance triangles"))
         return rc;
     // the weld: z, then (x, y), both stable, so equal positions end adjacent in ascending corner index
     HIP_TRY(rocprim::radix_sort_pairs(sc.temp, bytes, sc.zkey, sc.zsorted, sc.index, sc.zorder, (size_t)n, 0, 32, stream));
-    hipLaunchKernelGGL(sd_gather, dim3(grid_of(n)), dim3(kSdfBlock), 0, stream, n, (const uint64_t *)sc.xykey, (const uint32_t *)sc.zorder,
+    hipLaunchKernelGGL(sd_gather, dim3(grid_of(n, kSdfBlock)), dim3(kSdfBlock), 0, stream, n, (const uint64_t *)sc.xykey, (const uint32_t *)sc.zorder,
                        sc.xyg);
     bytes = sc.temp_bytes;
     HIP_TRY(rocprim::radix_sort_pairs(sc.temp, bytes, sc.xyg, sc.xys, sc.zorder, sc.order, (size_t)n, 0, 64, stream));
-    hipLaunchKernelGGL(sd_weld_heads, dim3(grid_of(n)), dim3(kSdfBlock), 0, stream, n, v.positions, (const uint32_t *)sc.order, sc.head);
+    hipLaunchKernelGGL(sd_weld_heads, dim3(grid_of(n, kSdfBlock)), dim3(kSdfBlock), 0, stream, n, v.positions, (const uint32_t *)sc.order, sc.head);
     bytes = sc.temp_bytes;
     HIP_TRY(rocprim::inclusive_scan(sc.temp, bytes, sc.head, sc.scan, (size_t)n, rocprim::plus<uint32_t>(), stream));
-    hipLaunchKernelGGL(sd_vertex_of_corner, dim3(grid_of(n)), dim3(kSdfBlock), 0, stream, n, (const uint32_t *)sc.order,
+    hipLaunchKernelGGL(sd_vertex_of_corner, dim3(grid_of(n, kSdfBlock)), dim3(kSdfBlock), 0, stream, n, (const uint32_t *)sc.order,
                        (const uint32_t *)sc.scan, sc.vertex);
-    hipLaunchKernelGGL(sd_vertex_normals, dim3(grid_of(n)), dim3(kSdfBlock), 0, stream, n, (const uint32_t *)sc.order,
+    hipLaunchKernelGGL(sd_vertex_normals, dim3(grid_of(n, kSdfBlock)), dim3(kSdfBlock), 0, stream, n, (const uint32_t *)sc.order,
                        (const uint32_t *)sc.head, (const float *)sc.alpha, sign, counts);
     if (const int rc = launched("signed-distance weld"))
         return rc;
     // the edges, in the weld's buffers (its keys are dead now): key, slot and from-vertex per slot, then the stable sort
     const int bits = edge_bits(n);
-    hipLaunchKernelGGL(sd_edge_keys, dim3(grid_of(nt)), dim3(kSdfBlock), 0, stream, nt, (const uint32_t *)sc.vertex, bits, sc.xykey,
+    hipLaunchKernelGGL(sd_edge_keys, dim3(grid_of(nt, kSdfBlock)), dim3(kSdfBlock), 0, stream, nt, (const uint32_t *)sc.vertex, bits, sc.xykey,
                        sc.index, sc.zkey);
     bytes = sc.temp_bytes;
     HIP_TRY(rocprim::radix_sort_pairs(sc.temp, bytes, sc.xykey, sc.xys, sc.index, sc.order, (size_t)n, 0, 2 * bits, stream));
-    hipLaunchKernelGGL(sd_edge_normals, dim3(grid_of(n)), dim3(kSdfBlock), 0, stream, n, (const uint64_t *)sc.xys, (const uint32_t *)sc.order,
+    hipLaunchKernelGGL(sd_edge_normals, dim3(grid_of(n, kSdfBlock)), dim3(kSdfBlock), 0, stream, n, (const uint64_t *)sc.xys, (const uint32_t *)sc.order,
                        (const uint32_t *)sc.zkey, sign, counts);
     return launched("signed-distance edges");
 }
@@ -376,10 +366,8 @@ int derive(SdfState &st, const SceneView &v, hipStream_t stream)
     return SHRAY_OK;
 }
 
-// The scene on its device, with this library's state, the sign data current on `stream`: derived there when it is stale
-// (the event recorded after it), else `stream` waits for the event of the derivation, which may have run on another
-// stream (no host synchronisation either way).  With `walk`, also the walk's refusals (the point query's) and its stack
-// height.
+// The scene on its device, with this library's state and the sign data current on `stream` (make_current).  With `walk`,
+// also the walk's refusals (the point query's) and its stack height.
 int prepare(shray_scene *scene, ShrayQueryScene *q, SdfState **out, hipStream_t stream, bool walk)
 {
     int rc = enter_scene(scene, q);
@@ -404,18 +392,8 @@ int prepare(shray_scene *scene, ShrayQueryScene *q, SdfState **out, hipStream_t 
         if ((rc = check_walkable(*q, st.height)))
             return rc;
     }
-    if (!st.derived || st.generation != generation) {
-        st.derived = false;
-        if ((rc = derive(st, q->view, stream)))
-            return rc;
-        HIP_TRY(hipEventRecord(st.done, stream));
-        st.derived = true;
-        st.generation = generation;
-    } else {
-        HIP_TRY(hipStreamWaitEvent(stream, st.done, 0));
-    }
     *out = &st;
-    return SHRAY_OK;
+    return make_current(st, generation, stream, [&] { return derive(st, q->view, stream); });
 }
 
 int signed_device(shray_scene *scene, const shray_point *d_points, int64_t count, float *d_signed, shray_closest *d_closest,
@@ -447,7 +425,7 @@ int signed_device(shray_scene *scene, const shray_point *d_points, int64_t count
         shray_closest *records = d_closest ? d_closest + first : (shray_closest *)scratch;
         rc = enqueue_closest(q, st->height, d_points + first, m, records, stream, nullptr);
         if (!rc) {
-            hipLaunchKernelGGL(sd_sign, dim3(grid_of(m)), dim3(kSdfBlock), 0, stream, m, (const float4 *)(d_points + first),
+            hipLaunchKernelGGL(sd_sign, dim3(grid_of(m, kSdfBlock)), dim3(kSdfBlock), 0, stream, m, (const float4 *)(d_points + first),
                                (const float4 *)records, sign, d_signed + first);
             rc = launched("signed-distance sign");
         }

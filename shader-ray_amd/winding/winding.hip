@@ -4,9 +4,10 @@
 // The node records are derived once per scene geometry, on the device, on the stream of the query that finds them stale:
 // the leaves first, one lane per leaf, then the branches bottom-up by HEIGHT as the refit builds its boxes (refit/refit.hip):
 // a branch of height h reads only records of lower heights, so each wide height is a launch of its own and the narrow rest
-// one workgroup that steps through them behind barriers.  The order by height and each node's topology come from one blocking
-// readback of octant copy 7 by the first call (a refit never changes the topology); after that a derivation reads nothing
-// back.  An event recorded after it orders it for other streams and for the download.
+// one workgroup that steps through them behind barriers.  The order by height, each node's topology and that schedule are
+// csrc/tree_order.h's, from one blocking readback of octant copy 7 by the first call (point/packed_walk.h; a refit never
+// changes the topology); after that a derivation reads nothing back.  When the records are stale, and the event recorded
+// after a derivation that orders it for other streams and for the download, are csrc/client_internal.h's DerivedState.
 //
 // A query is one lane per point in one-wave workgroups.  The walk's stack holds node names in LDS, level-major, one level per
 // edge of the tree's height.  A node costs one 16-byte load of { P, r } for the far-field test; a far node then loads N and M,
@@ -19,8 +20,6 @@
 #include <algorithm>
 #include <cmath>
 #include <memory>
-#include <utility>
-#include <vector>
 
 #include "client_internal.h"
 #include "point_walk.h"
@@ -37,13 +36,6 @@ constexpr uint64_t kChunk = 1ull << 22;   // points per scratch chunk when the c
 constexpr int kF = SHRAY_WINDING_DATA_FLOATS;
 constexpr float kInv4Pi = (float)(1.0 / (4.0 * 3.14159265358979323846));
 constexpr float kInv2Pi = (float)(1.0 / (2.0 * 3.14159265358979323846));
-
-inline unsigned int grid_of(uint64_t n, int block) { return (unsigned int)((n + block - 1) / block); }
-
-// topology of a packed node: a leaf {first triangle, count | kLeafFlag}, a branch {negative child, positive child} (indices)
-struct Topo {
-    uint32_t x, y;
-};
 
 // one node's record as the derivation builds it
 struct Moments {
@@ -306,96 +298,21 @@ __global__ void __launch_bounds__(kBlock) wn_signed(WindingView v, PointRange pr
     out[i] = (w > 0.5f && r0.w > 0.0f) ? -d : d;
 }
 
-// What this library keeps per scene: the topology in height order (from the first call's readback), the node records, the
-// geometry generation they were derived from, and an event recorded after the derivation.
-struct WindingState {
-    int height = -1;                      // edges from the root to the deepest leaf
-    uint32_t n = 0, leaves = 0, tail_height = 1, tallest = 0;
-    std::vector<uint32_t> height_start;   // order[height_start[h] .. height_start[h + 1]) have height h
-    bool derived = false;
-    uint64_t generation = 0;
-    DeviceBuffer order, topo, heights, data;
-    hipEvent_t done = nullptr;
-    ~WindingState()
-    {
-        if (done)
-            (void)hipEventDestroy(done);
-    }
+// What this library keeps per scene: the topology in height order (from the first call's readback), the node records, and
+// when they were derived (DerivedState).
+struct WindingState : DerivedState {
+    TreeOrder levels;         // (its per-node arrays are released once they are on the device)
+    DeviceTreeOrder tree;
+    DeviceBuffer data;
 };
 
-// The one blocking readback: copy 7's child words -> the topology, every node's height (a post-order walk from the root
-// that also proves each node is reached once), the order by height; uploaded with the record buffer and the event.
+// the one blocking readback (octant copy 7), its order by height onto the device, and the record buffer
 int build_state(const ShrayQueryScene &q, WindingState &st)
 {
-    const uint32_t n = q.view.packed_nodes_bytes / (uint32_t)sizeof(DeviceNode), nt = q.view.triangle_count;
-    std::vector<DeviceNode> copy(n);
-    const char *copy7 = static_cast<const char *>(q.view.packed_nodes) + (size_t)kOctant * q.view.packed_nodes_bytes;
-    HIP_TRY(hipMemcpy(copy.data(), copy7, q.view.packed_nodes_bytes, hipMemcpyDeviceToHost));
-    const uint32_t per = (uint32_t)(sizeof(DeviceNode) >> kNodeNameShift);
-    std::vector<Topo> topo(n);
-    for (uint32_t k = 0; k < n; k++) {
-        const DeviceNode &d = copy[k];
-        if (d.b & kLeafFlag) {
-            if ((uint64_t)d.a + (d.b & ~kLeafFlag) > nt)
-                return fail(SHRAY_ERR_BAD_TREE, "packed leaf %u names triangles beyond the scene's %u", k, nt);
-            topo[k] = {d.a, d.b};
-        } else {
-            const uint32_t neg = d.a & kChildNameMask, pos = d.b;   // copy 7 visits the negative child first
-            if (neg % per || pos % per || neg / per >= n || pos / per >= n)
-                return fail(SHRAY_ERR_BAD_TREE, "packed node %u names a child beyond the tree's %u nodes", k, n);
-            topo[k] = {neg / per, pos / per};
-        }
-    }
-    const uint32_t root = q.view.packed_root / per;
-    if (q.view.packed_root % per || root >= n)
-        return fail(SHRAY_ERR_BAD_TREE, "the packed root %u is not a node of %u", q.view.packed_root, n);
-    std::vector<uint32_t> height(n, 0);
-    std::vector<uint8_t> seen(n, 0);
-    std::vector<std::pair<uint32_t, bool>> todo{{root, false}};
-    uint32_t reached = 0, tallest = 0;
-    while (!todo.empty()) {
-        const auto [k, expanded] = todo.back();
-        todo.pop_back();
-        const bool leaf = topo[k].y & kLeafFlag;
-        if (!expanded) {
-            if (seen[k]++)
-                return fail(SHRAY_ERR_BAD_TREE, "packed node %u is reached twice", k);
-            reached++;
-            if (!leaf) {
-                todo.push_back({k, true});
-                todo.push_back({topo[k].x, false});
-                todo.push_back({topo[k].y, false});
-            }
-        } else {
-            height[k] = 1 + std::max(height[topo[k].x], height[topo[k].y]);
-            tallest = std::max(tallest, height[k]);
-        }
-    }
-    if (reached != n)
-        return fail(SHRAY_ERR_BAD_TREE, "the packed tree reaches %u of its %u nodes", reached, n);
-    st.height_start.assign(tallest + 2, 0);
-    for (uint32_t k = 0; k < n; k++)
-        st.height_start[height[k] + 1]++;
-    for (uint32_t h = 0; h <= tallest; h++)
-        st.height_start[h + 1] += st.height_start[h];
-    std::vector<uint32_t> order(n), next(st.height_start.begin(), st.height_start.end() - 1);
-    for (uint32_t k = 0; k < n; k++)
-        order[next[height[k]]++] = k;
-    st.n = n;
-    st.tallest = tallest;
-    st.leaves = st.height_start[1];
-    st.tail_height = 1;
-    while (st.tail_height <= tallest && st.height_start[st.tail_height + 1] - st.height_start[st.tail_height] > (uint32_t)kTailBlock)
-        st.tail_height++;
-    HIP_TRY(st.order.alloc((size_t)n * sizeof(uint32_t)));
-    HIP_TRY(st.topo.alloc((size_t)n * sizeof(Topo)));
-    HIP_TRY(st.heights.alloc(st.height_start.size() * sizeof(uint32_t)));
-    HIP_TRY(st.data.alloc((size_t)n * kF * sizeof(float)));
-    HIP_TRY(hipMemcpy(st.order.p, order.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(st.topo.p, topo.data(), (size_t)n * sizeof(Topo), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(st.heights.p, st.height_start.data(), st.height_start.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
-    st.height = (int)height[root];
+    int rc = packed_tree_order(q, kTailBlock, &st.levels);
+    if (rc || (rc = upload_tree_order(st.levels, st.tree, true, nullptr)))
+        return rc;
+    HIP_TRY(st.data.alloc((size_t)st.levels.height_start.back() * kF * sizeof(float)));   // (one record per node)
     return SHRAY_OK;
 }
 
@@ -403,34 +320,30 @@ int build_state(const ShrayQueryScene &q, WindingState &st)
 int derive(const WindingState &st, const SceneView &v, hipStream_t stream)
 {
     const DeviceNode *copy7 = reinterpret_cast<const DeviceNode *>(static_cast<const char *>(v.packed_nodes) + (size_t)kOctant * v.packed_nodes_bytes);
-    const uint32_t *order = st.order.as<const uint32_t>();
-    const Topo *topo = st.topo.as<const Topo>();
+    const uint32_t *order = st.tree.order.as<const uint32_t>();
+    const Topo *topo = st.tree.topo.as<const Topo>();
     float *data = st.data.as<float>();
-    if (st.leaves) {
-        hipLaunchKernelGGL(wn_leaves, dim3(grid_of(st.leaves, kDeriveBlock)), dim3(kDeriveBlock), 0, stream, st.leaves, order, topo, copy7,
-                           v.positions, data);
-        if (const int rc = launched("winding leaves"))
-            return rc;
-    }
-    for (uint32_t h = 1; h < st.tail_height; h++) {
-        const uint32_t begin = st.height_start[h], count = st.height_start[h + 1] - begin;
-        hipLaunchKernelGGL(wn_branches, dim3(grid_of(count, kDeriveBlock)), dim3(kDeriveBlock), 0, stream, begin, count, order, topo, copy7,
-                           data);
-        if (const int rc = launched("winding branches"))
-            return rc;
-    }
-    if (st.tail_height <= st.tallest) {
-        hipLaunchKernelGGL(wn_branches_tail, dim3(1), dim3(kTailBlock), 0, stream, st.heights.as<const uint32_t>(), st.tail_height,
-                           st.tallest + 1, order, topo, copy7, data);
-        if (const int rc = launched("winding branches (tail)"))
-            return rc;
-    }
-    return SHRAY_OK;
+    return for_each_level(
+        st.levels,
+        [&](uint32_t count) {
+            hipLaunchKernelGGL(wn_leaves, dim3(grid_of(count, kDeriveBlock)), dim3(kDeriveBlock), 0, stream, count, order, topo, copy7,
+                               v.positions, data);
+            return launched("winding leaves");
+        },
+        [&](uint32_t begin, uint32_t count) {
+            hipLaunchKernelGGL(wn_branches, dim3(grid_of(count, kDeriveBlock)), dim3(kDeriveBlock), 0, stream, begin, count, order, topo,
+                               copy7, data);
+            return launched("winding branches");
+        },
+        [&](uint32_t first_height, uint32_t heights) {
+            hipLaunchKernelGGL(wn_branches_tail, dim3(1), dim3(kTailBlock), 0, stream, st.tree.heights.as<const uint32_t>(), first_height,
+                               heights, order, topo, copy7, data);
+            return launched("winding branches (tail)");
+        });
 }
 
-// The scene on its device, with this library's state and the records current on `stream`: derived there when they are
-// stale (the event recorded after it), else `stream` waits for the event of the derivation, which may have run on another
-// stream.  The walk's refusals (the point query's) come before anything is launched.
+// The scene on its device, with this library's state and the records current on `stream` (make_current).  The walk's
+// refusals (the point query's) come before anything is launched.
 int prepare(shray_scene *scene, ShrayQueryScene *q, WindingState **out, hipStream_t stream)
 {
     int rc = enter_scene(scene, q);
@@ -449,20 +362,10 @@ int prepare(shray_scene *scene, ShrayQueryScene *q, WindingState **out, hipStrea
         *slot = st;
     }
     WindingState &st = *static_cast<WindingState *>(slot->get());
-    if ((rc = check_walkable(*q, st.height)))
+    if ((rc = check_walkable(*q, st.levels.height)))
         return rc;
-    if (!st.derived || st.generation != generation) {
-        st.derived = false;
-        if ((rc = derive(st, q->view, stream)))
-            return rc;
-        HIP_TRY(hipEventRecord(st.done, stream));
-        st.derived = true;
-        st.generation = generation;
-    } else {
-        HIP_TRY(hipStreamWaitEvent(stream, st.done, 0));
-    }
     *out = &st;
-    return SHRAY_OK;
+    return make_current(st, generation, stream, [&] { return derive(st, q->view, stream); });
 }
 
 // the checks every query makes before it touches a scene
@@ -498,7 +401,7 @@ int number_device(shray_scene *scene, const shray_point *d_points, int64_t count
         return rc;
     const WindingView v = view_of(q, *st, beta);
     PointRange pr{(const float4 *)d_points, (uint64_t)count, 0};
-    const size_t lds = (size_t)kBlock * (size_t)std::max(st->height, 1) * sizeof(uint32_t);
+    const size_t lds = (size_t)kBlock * (size_t)std::max(st->levels.height, 1) * sizeof(uint32_t);
     return for_each_launch(((uint64_t)count + kBlock - 1) / kBlock, kPointsPerLaunch / kBlock, [&](uint64_t first, dim3 grid) {
         pr.first = first * kBlock;
         hipLaunchKernelGGL(wn_query, grid, dim3(kBlock), lds, stream, v, pr, d_out);
@@ -522,7 +425,7 @@ int signed_device(shray_scene *scene, const shray_point *d_points, int64_t count
         return rc;
     const WindingView v = view_of(q, *st, beta);
     const uint64_t n = (uint64_t)count;
-    const size_t lds = (size_t)kBlock * (size_t)std::max(st->height, 1) * sizeof(uint32_t);
+    const size_t lds = (size_t)kBlock * (size_t)std::max(st->levels.height, 1) * sizeof(uint32_t);
     // the closest-point walk, then the sign, a launch's worth of points at a time; without the caller's records, through
     // stream-ordered scratch of at most kChunk records
     const uint64_t chunk = d_closest ? kPointsPerLaunch : std::min(n, kChunk);
@@ -532,7 +435,7 @@ int signed_device(shray_scene *scene, const shray_point *d_points, int64_t count
     for (uint64_t first = 0; first < n && !rc; first += chunk) {
         const uint64_t m = std::min(chunk, n - first);
         shray_closest *records = d_closest ? d_closest + first : (shray_closest *)scratch;
-        rc = enqueue_closest(q, st->height, d_points + first, m, records, stream, nullptr);
+        rc = enqueue_closest(q, st->levels.height, d_points + first, m, records, stream, nullptr);
         if (!rc) {
             const PointRange pr{(const float4 *)(d_points + first), m, 0};
             hipLaunchKernelGGL(wn_signed, dim3(grid_of(m, kBlock)), dim3(kBlock), lds, stream, v, pr, (const float4 *)records,
@@ -611,7 +514,7 @@ int shray_scene_winding_data_download(shray_scene *scene, float *out)
     if (rc)
         return rc;
     HIP_TRY(hipEventSynchronize(st->done));   // the derivation may have run on any stream
-    HIP_TRY(hipMemcpy(out, st->data.p, (size_t)st->n * kF * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, st->data.p, st->data.bytes, hipMemcpyDeviceToHost));
     return SHRAY_OK;
 }
 
