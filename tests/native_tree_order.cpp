@@ -1,5 +1,5 @@
 // The checks of tests/test_tree_order_cpu.py on csrc/tree_order.h: hand-built DeviceNode arrays in both octant conventions
-// against a plain recursive height computation.  Usage: native_tree_order shapes | random SEED COUNT | refusals.
+// against a plain recursive height computation.  Usage: native_tree_order shapes | edges | random SEED COUNT | refusals.
 // Prints one line per failed check and exits 1, or "ok" and exits 0.
 #include <algorithm>
 #include <cstdio>
@@ -207,6 +207,98 @@ void shapes()
     }
 }
 
+// a new root over two trees: node 0, then `neg`'s nodes, then `pos`'s (their roots must be their node 0)
+Plain join(const Plain &neg, const Plain &pos)
+{
+    Plain t;
+    t.nodes.push_back({false, 1, 1 + (uint32_t)neg.nodes.size(), 0});
+    const auto append = [&](const Plain &from) {
+        const uint32_t nodes = (uint32_t)t.nodes.size(), triangles = t.triangles;
+        for (Plain::Node n : from.nodes) {
+            if (n.leaf)
+                n.x += triangles;
+            else
+                n.x += nodes, n.y += nodes;
+            t.nodes.push_back(n);
+        }
+        t.triangles += from.triangles;
+    };
+    append(neg);
+    append(pos);
+    return t;
+}
+
+// The schedule of a tree shaped to its edges (tests/tree_shapes.py builds the same shapes for the GPU tests): the leaves, the
+// tallest height, where the tail starts, and exactly the wide(begin, count) and tail(first, heights) calls for_each_level
+// makes for a tail of kTailWidth threads.
+void check_schedule(const Plain &t, const char *what, uint32_t leaves, uint32_t tallest, uint32_t tail_height,
+                    const std::vector<uint32_t> &wide_counts)
+{
+    check_tree(t, what);
+    const uint32_t n = (uint32_t)t.nodes.size();
+    for (int octant : {0, 7}) {
+        TreeOrder r;
+        const std::string refused = tree_order(encode(t, octant).data(), n, t.root * kPer, t.triangles, octant, kTailWidth, &r);
+        CHECK(refused.empty(), "%s, copy %d: %s", what, octant, refused.c_str());
+        if (!refused.empty())
+            return;
+        CHECK(r.leaves == leaves && r.tallest == tallest && r.height == (int)tallest && r.tail_height == tail_height,
+              "%s, copy %d: %u leaves, tallest %u, height %d, tail_height %u", what, octant, r.leaves, r.tallest, r.height, r.tail_height);
+        CHECK(r.height_start.size() == tallest + 2, "%s, copy %d: %zu entries of height_start", what, octant, r.height_start.size());
+        std::vector<std::pair<uint32_t, uint32_t>> wide, tail;
+        uint32_t leaf_calls = 0, leaf_count = 0;
+        const int rc = for_each_level(
+            r, [&](uint32_t count) { return leaf_calls++, leaf_count = count, 0; },
+            [&](uint32_t begin, uint32_t count) { return wide.push_back({begin, count}), 0; },
+            [&](uint32_t first, uint32_t heights) { return tail.push_back({first, heights}), 0; });
+        CHECK(rc == 0 && leaf_calls == 1 && leaf_count == leaves, "%s, copy %d: the leaves' call", what, octant);
+        CHECK(wide.size() == wide_counts.size(), "%s, copy %d: %zu wide calls, expected %zu", what, octant, wide.size(), wide_counts.size());
+        uint32_t begin = leaves;
+        for (size_t i = 0; i < wide.size() && i < wide_counts.size(); i++) {
+            CHECK(wide[i].first == begin && wide[i].second == wide_counts[i], "%s, copy %d: wide call %zu is (%u, %u), expected (%u, %u)",
+                  what, octant, i, wide[i].first, wide[i].second, begin, wide_counts[i]);
+            begin += wide_counts[i];
+        }
+        if (tail_height <= tallest) {
+            CHECK(tail.size() == 1 && tail[0].first == tail_height && tail[0].second == tallest + 1,
+                  "%s, copy %d: %zu tail calls, the first (%u, %u)", what, octant, tail.size(), tail.empty() ? 0 : tail[0].first,
+                  tail.empty() ? 0 : tail[0].second);
+            // the tail picks up where the wide launches stopped, and its first height fits the workgroup
+            CHECK(r.height_start[tail_height] == begin && r.height_start[tail_height + 1] - begin <= kTailWidth, "%s, copy %d: the tail's start",
+                  what, octant);
+        } else {
+            CHECK(tail.empty(), "%s, copy %d: a tail call for a tree without a tail", what, octant);
+        }
+    }
+}
+
+void edge_shapes()
+{
+    const auto halves = [](uint32_t leaves) { return leaves / 2; };
+    const auto perfect = [&](int k) { return tree_of(1u << k, halves); };
+    check_schedule(perfect(1), "one_branch", 2, 1, 1, {});
+    check_schedule(perfect(11), "tail_full", 2048, 11, 1, {});                       // height 1: exactly 1024
+    check_schedule(join(perfect(11), perfect(1)), "wide_by_one", 2050, 12, 2, {1025});
+    check_schedule(perfect(13), "two_wide", 8192, 13, 3, {4096, 2048});              // height 3: exactly 1024
+    Plain spine = perfect(0);
+    for (int i = 0; i < 13; i++)
+        spine = join(perfect(i), spine);
+    check_schedule(spine, "lopsided", 8192, 13, 3, {4096, 2048});
+    spine = perfect(12);
+    for (int k : {1, 2, 1, 2})
+        spine = join(perfect(k), spine);
+    check_schedule(spine, "mixed_spine", 4108, 16, 3, {2054, 1026});
+    {
+        // the widths the shapes are built around
+        TreeOrder r;
+        const Plain t = perfect(11), w = join(perfect(11), perfect(1));
+        tree_order(encode(t, 0).data(), (uint32_t)t.nodes.size(), 0, t.triangles, 0, kTailWidth, &r);
+        CHECK(r.height_start[2] - r.height_start[1] == kTailWidth, "tail_full: %u branches of height 1", r.height_start[2] - r.height_start[1]);
+        tree_order(encode(w, 0).data(), (uint32_t)w.nodes.size(), 0, w.triangles, 0, kTailWidth, &r);
+        CHECK(r.height_start[2] - r.height_start[1] == kTailWidth + 1, "wide_by_one: %u branches of height 1", r.height_start[2] - r.height_start[1]);
+    }
+}
+
 void random_trees(uint32_t seed, int count)
 {
     std::mt19937 rng(seed);
@@ -268,6 +360,8 @@ int main(int argc, char **argv)
     const std::string what = argc > 1 ? argv[1] : "";
     if (what == "shapes")
         shapes();
+    else if (what == "edges")
+        edge_shapes();
     else if (what == "random" && argc == 4)
         random_trees((uint32_t)atoi(argv[2]), atoi(argv[3]));
     else if (what == "refusals")

@@ -31,6 +31,12 @@ def test_the_named_shapes(exe):
     run(exe, "shapes")
 
 
+def test_the_shapes_at_the_schedules_edges(exe):
+    """tests/tree_shapes.py's one_branch, tail_full, wide_by_one, two_wide, lopsided and mixed_spine, built by the program itself:
+    leaves, tallest, tail_height and exactly the wide and tail calls for_each_level makes for a tail of 1024 threads"""
+    run(exe, "edges")
+
+
 @pytest.mark.parametrize("seed", [1, 77, 2024])
 def test_seeded_random_trees(exe, seed):
     run(exe, "random", str(seed), "120")

@@ -197,6 +197,17 @@ class Restated:
             lo, hi = boxes[:, :3], boxes[:, 3:]
         self.records = node_records(self.tree, lo, hi, self.positions)
 
+    @classmethod
+    def of_tree(cls, tree: TreeArrays, positions, boxes) -> "Restated":
+        """the same from a tree that no world holds: its pre-order arrays, the corners float32 [T * 9] in the tree's triangle
+        order and the node boxes float32 [n, 6] in pre-order"""
+        self = cls.__new__(cls)
+        self.tree = tree
+        self.positions = np.asarray(positions, F).reshape(-1)
+        boxes = np.asarray(boxes, F).reshape(-1, 6)
+        self.records = node_records(tree, boxes[:, :3], boxes[:, 3:], self.positions)
+        return self
+
     def w(self, points, beta=2.0):
         return winding(self.tree, self.records, self.positions, points, beta)
 
