@@ -22,6 +22,7 @@ MULTIHIT_LIB = os.path.join(PKG_DIR, "libshray_multihit.so")
 INSTANCE_MULTIHIT_LIB = os.path.join(PKG_DIR, "libshray_instance_multihit.so")
 # SHRAY_NEAR_LIB selects an experiment build of the same library (profiles/near_bench.py --ab); unset in normal use
 NEAR_LIB = os.environ.get("SHRAY_NEAR_LIB") or os.path.join(PKG_DIR, "libshray_near.so")
+OVERLAP_LIB = os.path.join(PKG_DIR, "libshray_overlap.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
 HIP_LIB = os.environ.get("SHRAY_HIP_LIB") or os.path.join(PKG_DIR, "libshray_hip.so")
 
@@ -407,6 +408,29 @@ NEAR_SYMBOLS = [
                                                 C.POINTER(Counters)]),
 ]
 
+# include/shader_ray_overlap.h -----------------------------------------------------------------------------
+OVERLAP_MAX = 64
+OVERLAP_ANY = 1
+
+
+class Box(C.Structure):
+    """shray_box: an axis-aligned box, lo and hi with a pad after each (32 bytes)."""
+    _fields_ = [("lo", C.c_float * 3), ("pad0", C.c_float), ("hi", C.c_float * 3), ("pad1", C.c_float)]
+
+
+class OverlapParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_triangles", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
+OVERLAP_SYMBOLS = [
+    ("shray_overlap_params_init", None, [C.POINTER(OverlapParams)]),
+    ("shray_overlap_triangles_device", C.c_int, [C.c_void_p, C.POINTER(OverlapParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]),
+    ("shray_overlap_triangles", C.c_int, [C.c_void_p, C.POINTER(OverlapParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("shray_overlap_triangles_counters", C.c_int, [C.c_void_p, C.POINTER(OverlapParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(Counters)]),
+]
+
 # include/shader_ray_instance_multihit.h -------------------------------------------------------------------
 INSTANCE_MULTIHIT_SYMBOLS = [
     ("shray_trace_instances_all_hits_device", C.c_int, [C.c_void_p, C.POINTER(MultihitParams), C.c_void_p, C.c_int64, C.c_void_p,
@@ -513,6 +537,11 @@ def load_multihit():
 def load_near():
     """Loads the within-radius query library (libshray_near.so)."""
     return _load_client(NEAR_LIB, NEAR_SYMBOLS)
+
+
+def load_overlap():
+    """Loads the box-overlap query library (libshray_overlap.so)."""
+    return _load_client(OVERLAP_LIB, OVERLAP_SYMBOLS)
 
 
 def load_instance_multihit():

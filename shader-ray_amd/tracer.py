@@ -440,6 +440,90 @@ class Scene:
         host points, a tensor for GPU points."""
         return self.triangles_within(points, max_near=0, counts=True)[1]
 
+    def triangles_in_boxes(self, boxes, max_triangles: int = 8, counts: bool = True, counters: bool = False, any_only: bool = False):
+        """Box-overlap queries (include/shader_ray_overlap.h): per axis-aligned box the number of triangles that touch it and
+        the `max_triangles` smallest of their indices in ascending order, the other slots SHRAY_HIT_MISS (-1).  `boxes`: a
+        BOX_DTYPE array or [n, 6] (lo, hi) / [n, 8] (the shray_box layout) float32 takes the blocking host path
+        (shray_overlap_triangles) and returns (indices: int32 [n, max_triangles], counts: int32 [n]); a float32 [n, 6] / [n, 8]
+        GPU tensor on the scene's device takes the device path (shray_overlap_triangles_device) on the current torch stream
+        and returns tensors of the same shapes.  counts=False returns None for the counts; max_triangles = 0 returns None for
+        the indices.  any_only=True (with max_triangles = 0) sets SHRAY_OVERLAP_ANY: the count is 1 or 0 and the walk stops at
+        the first touching triangle.  counters=True (host boxes only) also returns the walk's counters
+        (shray_overlap_triangles_counters)."""
+        if max_triangles == 0 and not counts:
+            raise ValueError("nothing is asked for: max_triangles is 0 and counts is False")
+        lib = N.load_overlap()
+        op = overlap_params(max_triangles, any_only)
+        boxes = _host_if_cpu(boxes)
+        if _is_torch(boxes):
+            import torch
+            if counters:
+                raise ValueError("counters are counted on the host path: pass host boxes")
+            bx = self._device_boxes(boxes)
+            out = torch.empty((len(bx), max_triangles), dtype=torch.int32, device=bx.device) if max_triangles > 0 else None
+            cnt = torch.empty(len(bx), dtype=torch.int32, device=bx.device) if counts else None
+            stream = torch.cuda.current_stream(bx.device)
+            bx.record_stream(stream)   # (the query reads it after this call returns)
+            N.check(lib.shray_overlap_triangles_device(self._handle, C.byref(op), C.c_void_p(bx.data_ptr()), len(bx),
+                                                       C.c_void_p(out.data_ptr() if out is not None else None),
+                                                       C.c_void_p(cnt.data_ptr() if counts else None), C.c_void_p(stream.cuda_stream)))
+            return out, cnt
+        bx = _host_boxes(boxes)
+        out = np.empty((len(bx), max_triangles), np.int32) if max_triangles > 0 else None   # (the library refuses a negative one)
+        cnt = np.empty(len(bx), np.int32) if counts else None
+        args = (self._handle, C.byref(op), bx.ctypes.data_as(C.c_void_p), len(bx),
+                out.ctypes.data_as(C.c_void_p) if out is not None else None, cnt.ctypes.data_as(C.c_void_p) if counts else None)
+        if counters:
+            c = N.Counters()
+            N.check(lib.shray_overlap_triangles_counters(*args, C.byref(c)))
+            return out, cnt, c.as_dict()
+        N.check(lib.shray_overlap_triangles(*args))
+        return out, cnt
+
+    def _device_boxes(self, boxes):
+        """a float32 [n, 6] / [n, 8] GPU tensor on the scene's device as a contiguous [n, 8] shray_box tensor"""
+        import torch
+        if boxes.device.index != self.device_index():
+            raise ValueError(f"boxes are on {boxes.device}, the scene on cuda:{self.device_index()}")
+        if boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] not in (6, 8):
+            raise ValueError("a GPU box tensor must be float32 [n, 6] (lo, hi) or [n, 8] (the shray_box layout)")
+        if boxes.shape[1] == 8:
+            return boxes.contiguous()
+        bx = torch.zeros((len(boxes), 8), dtype=torch.float32, device=boxes.device)
+        bx[:, 0:3] = boxes[:, 0:3]
+        bx[:, 4:7] = boxes[:, 3:6]
+        return bx
+
+    def triangles_in_boxes_into(self, boxes_ptr: int, count: int, out_ptr: int, counts_ptr: int = 0, max_triangles: int = 8,
+                                any_only: bool = False, stream_ptr: int = 0):
+        """Asynchronous box-overlap queries on device memory of the scene's device (shray_overlap_triangles_device): `count`
+        shray_box records at `boxes_ptr` -> count * max_triangles int32 indices at `out_ptr` (0 iff max_triangles is 0) and,
+        unless `counts_ptr` is 0, `count` int32 counts there, on a HIP stream (`stream_ptr`)."""
+        op = overlap_params(max_triangles, any_only)
+        N.check(N.load_overlap().shray_overlap_triangles_device(self._handle, C.byref(op), C.c_void_p(boxes_ptr), count,
+                                                                C.c_void_p(out_ptr or None), C.c_void_p(counts_ptr or None),
+                                                                C.c_void_p(stream_ptr)))
+
+    def box_counts(self, boxes):
+        """How many triangles touch each box (triangles_in_boxes with max_triangles = 0): int32 [n], numpy for host boxes, a
+        tensor for GPU boxes."""
+        return self.triangles_in_boxes(boxes, max_triangles=0, counts=True)[1]
+
+    def boxes_touched(self, boxes):
+        """Whether any triangle touches each box (SHRAY_OVERLAP_ANY: the walk stops at the first one): bool [n], numpy for
+        host boxes, a tensor for GPU boxes."""
+        return self.triangles_in_boxes(boxes, max_triangles=0, counts=True, any_only=True)[1] != 0
+
+    def surface_voxels(self, origin, cell, dims, device=None):
+        """The occupancy grid of the surface: bool [nx, ny, nz], voxel (i, j, k) set iff a triangle touches the box
+        lo = origin + (i, j, k) * cell, hi = origin + (i + 1, j + 1, k + 1) * cell.  Each bound is one fp32 multiply and one
+        add, by the same expression for a face two voxels share, so neighbours share a bit-identical plane.  `cell`: a scalar
+        or three floats.  device=None builds the boxes with numpy and takes the host path; a torch device (the scene's)
+        builds them there with torch and returns a tensor.  The query is boxes_touched."""
+        boxes = voxel_boxes(origin, cell, dims, device)
+        nx, ny, nz = (int(d) for d in dims)
+        return self.boxes_touched(boxes).reshape(nx, ny, nz)
+
     def primary_hits(self, params: N.FrameParams, width: int, height: int) -> np.ndarray:
         """The hit of every pixel's 1-spp primary ray (shray_primary_hits_device): HIT_DTYPE [height, width], row 0 = bottom."""
         import torch
@@ -621,6 +705,58 @@ def near_params(max_near: int = 8) -> N.NearParams:
     return np_
 
 
+def overlap_params(max_triangles: int = 8, any_only: bool = False) -> N.OverlapParams:
+    op = N.OverlapParams()
+    N.load_overlap().shray_overlap_params_init(C.byref(op))
+    op.max_triangles = max_triangles
+    op.flags = N.OVERLAP_ANY if any_only else 0
+    return op
+
+
+# a box buffer of the box-overlap query (include/shader_ray_overlap.h): 32 bytes per element
+BOX_DTYPE = np.dtype([("lo", np.float32, 3), ("pad0", np.float32), ("hi", np.float32, 3), ("pad1", np.float32)])
+
+
+def make_boxes(lo, hi) -> np.ndarray:
+    """A BOX_DTYPE array from [n, 3] lower and upper corners."""
+    lo = np.asarray(lo, np.float32).reshape(-1, 3)
+    out = np.zeros(len(lo), BOX_DTYPE)
+    out["lo"] = lo
+    out["hi"] = np.asarray(hi, np.float32).reshape(-1, 3)
+    return out
+
+
+def _host_boxes(boxes) -> np.ndarray:
+    """Scene.triangles_in_boxes's host box forms as one contiguous BOX_DTYPE array."""
+    return _host_records(boxes, BOX_DTYPE, 6, 8, lambda a: make_boxes(a[:, 0:3], a[:, 3:6]), None, None,
+                         "boxes must be a BOX_DTYPE array or [n, 6] (lo, hi) / [n, 8] (shray_box) float32")
+
+
+def voxel_boxes(origin, cell, dims, device=None):
+    """Scene.surface_voxels's boxes in grid order (k fastest): plane i of an axis is origin + i * cell in fp32, one multiply and
+    one add; a voxel's lo and hi are two neighbouring planes.  A BOX_DTYPE array, or with `device` a float32 [n, 8] tensor."""
+    nx, ny, nz = (int(d) for d in dims)
+    if min(nx, ny, nz) < 1:
+        raise ValueError("dims must be three positive integers")
+    origin = np.asarray(origin, np.float32).reshape(3)
+    cell = np.broadcast_to(np.asarray(cell, np.float32), (3,))
+    if device is None:
+        planes = [origin[a] + np.arange(n + 1, dtype=np.float32) * cell[a] for a, n in enumerate((nx, ny, nz))]
+        out = np.zeros((nx, ny, nz), BOX_DTYPE)
+        for a, shape in enumerate(((nx, 1, 1), (1, ny, 1), (1, 1, nz))):
+            out["lo"][..., a] = planes[a][:-1].reshape(shape)
+            out["hi"][..., a] = planes[a][1:].reshape(shape)
+        return out.reshape(-1)
+    import torch
+    out = torch.zeros((nx, ny, nz, 8), dtype=torch.float32, device=device)
+    for a, (n, shape) in enumerate(((nx, (nx, 1, 1)), (ny, (1, ny, 1)), (nz, (1, 1, nz)))):
+        steps = torch.arange(n + 1, dtype=torch.float32, device=device) * float(cell[a])
+        planes = steps + float(origin[a])
+        out[..., a] = planes[:-1].reshape(shape)
+        out[..., 4 + a] = planes[1:].reshape(shape)
+    return out.reshape(-1, 8)
+
+
 class DeviceFlat:
     """get_shader_data on the GPU (shray_flatten_device): the flattened arrays of a host-built BVH, resident
     on the device.  `download()` gives a SceneDesc with host pointers (owned by this object)."""
@@ -763,6 +899,27 @@ class DeviceWorld:
     def near_counts(self, points):
         """Scene.near_counts on this scene."""
         return self.scene.near_counts(points)
+
+    def triangles_in_boxes(self, boxes, **kwargs):
+        """Scene.triangles_in_boxes on this scene."""
+        return self.scene.triangles_in_boxes(boxes, **kwargs)
+
+    def triangles_in_boxes_into(self, boxes_ptr: int, count: int, out_ptr: int, counts_ptr: int = 0, max_triangles: int = 8,
+                                any_only: bool = False, stream_ptr: int = 0):
+        """Scene.triangles_in_boxes_into on this scene."""
+        return self.scene.triangles_in_boxes_into(boxes_ptr, count, out_ptr, counts_ptr, max_triangles, any_only, stream_ptr)
+
+    def box_counts(self, boxes):
+        """Scene.box_counts on this scene."""
+        return self.scene.box_counts(boxes)
+
+    def boxes_touched(self, boxes):
+        """Scene.boxes_touched on this scene."""
+        return self.scene.boxes_touched(boxes)
+
+    def surface_voxels(self, origin, cell, dims, device=None):
+        """Scene.surface_voxels on this scene."""
+        return self.scene.surface_voxels(origin, cell, dims, device)
 
     def signed_distance(self, points, **kwargs):
         """Scene.signed_distance on this scene."""
