@@ -52,7 +52,13 @@
  * Coordinate range.  Measured on meshes whose largest coordinate is 1.7, scaled with their boxes by S = 2^k
  * (tests/test_overlap_reference.py): the set of every box is the unscaled one for -27 <= k <= 44.  Below,
  * the products of the plane and edge stages (the cube of a coordinate difference) lose bits to underflow; above, they
- * overflow.  Outside the range the contract above still holds bit for bit: the set is what the arithmetic above gives.
+ * overflow.  Outside the range the contract above still holds bit for bit: the set is what the arithmetic above gives
+ * (tests/test_gpu_overlap_scale.py runs it from 2^-90 to 2^67).  What a caller then sees, on those meshes: the set stays
+ * within stage 0's (the triangles whose vertex box meets the box), and it is NOT conservative: pairs are both gained and lost
+ * at 2^-70, 2^-40 and 2^45 (products that lost bits, or one overflowed product beside a finite one, do separate) and from
+ * 2^66 up, where the edge products overflow too.  It is a superset of the in-range set only where the plane alone has dropped
+ * out (its products are 0, or infinite and NaN) and the edge axes work as before: at 2^-64, and at 2^50 and 2^64; and at
+ * 2^-90, where every product of stages 1 and 2 is 0 and the set is exactly stage 0's.
  *
  * Errors: count == 0 is a no-op.  A wrong struct_size, K outside [0, SHRAY_OVERLAP_MAX], unknown flag bits, a nonzero
  * reserved field, SHRAY_OVERLAP_ANY with K != 0 or without counts, K == 0 together with no counts (nothing is asked for; with

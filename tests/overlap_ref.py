@@ -9,6 +9,8 @@ over triangles (and over blocks of boxes).
                                   (-1) when none does, UNWALKED (13) for every pair of a box that is not walked
   overlaps(positions, boxes)   -> bool [n_boxes, n_triangles]
   overlap(positions, boxes, k) -> (int32 [n_boxes, k], int32 [n_boxes]): the k smallest indices then -1, and the count
+  walk_counters(tree, node_boxes, corners, boxes, any_only) -> the walk's own work per box: node visits,
+                                  leaf visits, triangle tests and the greatest stack depth
 """
 import numpy as np
 
@@ -129,3 +131,65 @@ def from_set(member, k):
 
 def overlap(positions, boxes, k):
     return from_set(overlaps(positions, boxes), k)
+
+
+COUNTERS = ("node_visits", "leaf_visits", "triangle_tests")
+
+
+def walk_counters(tree, node_boxes, corners, boxes, any_only=False, member=None):
+    """The walk itself, one box at a time in plain python: over a refit_ref.TreeArrays `tree` (pre-order) whose
+    nodes' boxes are `node_boxes` float32 [n, 6] (refit_ref.node_boxes: the min/max fold the scene stores), the triangles being
+    `corners` [T, 3, 3] in the tree's order.  A node is entered iff the six comparisons pass; the root is tested once, both
+    children of an entered branch are tested (two node visits), the walk descends into the negative child when it overlaps and
+    pushes the positive one when both do, else into the positive one, else it pops; every triangle of a visited leaf is tested,
+    in index order; with `any_only` the walk ends at the first triangle that touches.  A box that is not walked visits nothing.
+
+    `member` is overlaps(corners, boxes) where the caller holds it already (only `any_only` looks at it).
+    Returns a dict of int64 [n_boxes]: node_visits, leaf_visits, triangle_tests and `stack`, the greatest number of stack
+    entries held at once."""
+    lo, hi = lo_hi(boxes)
+    go = walked(boxes)
+    if any_only and member is None:
+        member = overlaps(corners, boxes)
+    nb = np.asarray(node_boxes, F).reshape(-1, 6).tolist()
+    negative, positive = tree.negative.tolist(), tree.positive.tolist()
+    start, count = tree.start.tolist(), tree.triangles.tolist()
+    out = {name: np.zeros(len(lo), np.int64) for name in COUNTERS + ("stack",)}
+
+    for b in range(len(lo)):
+        if not go[b]:
+            continue
+        l0, l1, l2 = lo[b].tolist()
+        h0, h1, h2 = hi[b].tolist()
+
+        def enters(k):
+            x = nb[k]
+            return not (x[3] < l0 or x[0] > h0 or x[4] < l1 or x[1] > h1 or x[5] < l2 or x[2] > h2)
+
+        nodes, leaves, tests, deepest = 1, 0, 0, 0
+        stack = []
+        cur = 0 if enters(0) else -1
+        while cur >= 0:
+            nxt = -1
+            if negative[cur] < 0:
+                leaves += 1
+                if any_only:
+                    row = member[b, start[cur]:start[cur] + count[cur]]
+                    hit = np.flatnonzero(row)
+                    tests += int(hit[0]) + 1 if len(hit) else count[cur]
+                    if len(hit):
+                        break
+                else:
+                    tests += count[cur]
+            else:
+                nodes += 2
+                in0, in1 = enters(negative[cur]), enters(positive[cur])
+                if in0 and in1:
+                    stack.append(positive[cur])
+                    deepest = max(deepest, len(stack))
+                nxt = negative[cur] if in0 else positive[cur] if in1 else -1
+            if nxt < 0 and stack:
+                nxt = stack.pop()
+            cur = nxt
+        out["node_visits"][b], out["leaf_visits"][b], out["triangle_tests"][b], out["stack"][b] = nodes, leaves, tests, deepest
+    return out

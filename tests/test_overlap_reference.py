@@ -180,3 +180,88 @@ def test_the_scale_range_is_the_measured_one(pkg):
         kept = {name: set_kept_at(pkg, name, k) for name in SCALE_SCENES}
         print(f"k = {k}: set kept {kept}")
         assert not all(kept.values()), k
+
+
+# the walk's restatement (overlap_ref.walk_counters) ------------------------------------------------------------------------------
+
+def two_leaf_tree():
+    """test_gpu_uniform_leaf.two_leaf_scene as arrays: a branch over a leaf of 3 and a leaf of 5 triangles, its hand-made boxes"""
+    import refit_ref
+    left = [[[-6, -5, z], [0.2, -5, z], [-3, 5, z]] for z in (-0.5, 0.25, -1.0)]
+    right = [[[-0.2, -5, z], [6, -5, z], [3, 5, z]] for z in (0.0, -0.75, 0.5, -0.25, -1.5)]
+    i32 = lambda *x: np.array(x, np.int32)
+    tree = refit_ref.TreeArrays(i32(-1, 0, 0), i32(1, -1, -1), i32(2, -1, -1), None, None, i32(0, 0, 3), i32(0, 3, 5), None)
+    boxes = np.array([[-6.5, -6, -2, 6.5, 6, 1], [-6.5, -6, -2, 0.25, 6, 1], [-0.25, -6, -2, 6.5, 6, 1]], F)
+    return tree, boxes, np.asarray(left + right, F)
+
+
+def test_walk_counters_by_hand_on_the_two_leaf_tree():
+    tree, node_boxes, corners = two_leaf_tree()
+    # the band both leaves share, the left leaf, the right leaf, beside the root, and an inverted box
+    band = OR.make_boxes([(-0.1, -5.0, -2.0), (-6.0, -4.0, -2.0), (0.5, -4.0, -2.0), (7.0, 0.0, 0.0), (1.0, 0.0, 0.0)],
+                         [(0.1, -4.75, 1.0), (-4.0, -3.0, 1.0), (4.0, -3.0, 1.0), (8.0, 1.0, 1.0), (0.0, 1.0, 1.0)])
+    member = OR.overlaps(corners.reshape(-1), band)
+    assert member.sum(1).tolist() == [8, 3, 5, 0, 0]
+    c = OR.walk_counters(tree, node_boxes, corners, band)
+    assert c["node_visits"].tolist() == [3, 3, 3, 1, 0]      # the root, then both children of an entered branch; nothing unwalked
+    assert c["leaf_visits"].tolist() == [2, 1, 1, 0, 0]
+    assert c["triangle_tests"].tolist() == [8, 3, 5, 0, 0]
+    assert c["stack"].tolist() == [1, 0, 0, 0, 0]             # the positive leaf waits only where both overlap
+    a = OR.walk_counters(tree, node_boxes, corners, band, any_only=True)
+    assert member[0, 0] and member[1, 0] and member[2, 3]     # the first triangle of the first leaf entered touches
+    assert a["node_visits"].tolist() == [3, 3, 3, 1, 0] and a["leaf_visits"].tolist() == [1, 1, 1, 0, 0]
+    assert a["triangle_tests"].tolist() == [1, 1, 1, 0, 0] and a["stack"].tolist() == [1, 0, 0, 0, 0]
+    # ANY walks on while nothing touches: a box in the left leaf's node box, under its triangles (z = -1.75), touches none
+    under = OR.make_boxes([(-5.0, -4.0, -1.9)], [(-4.0, -3.0, -1.75)])
+    assert not OR.overlaps(corners.reshape(-1), under).any()
+    a = OR.walk_counters(tree, node_boxes, corners, under, any_only=True)
+    assert (a["node_visits"][0], a["leaf_visits"][0], a["triangle_tests"][0]) == (3, 1, 3)
+
+
+def test_walk_counters_on_a_root_that_is_a_leaf():
+    import tree_shapes
+    tree, vd = tree_shapes.build("leaf_root")
+    corners = vd[tree.triangle_vertices][:, :, :3]
+    root = tree.box[0]
+    boxes = OR.make_boxes([root[:3], root[3:] + F(1), (np.nan, 0, 0)], [root[3:], root[3:] + F(2), (1, 1, 1)])
+    member = OR.overlaps(corners.reshape(-1), boxes)
+    assert member.sum(1).tolist() == [3, 0, 0]
+    for any_only, tests in ((False, 3), (True, 1)):
+        c = OR.walk_counters(tree, tree.box, corners, boxes, any_only=any_only, member=member)
+        assert c["node_visits"].tolist() == [1, 1, 0] and c["leaf_visits"].tolist() == [1, 0, 0]
+        assert c["triangle_tests"].tolist() == [tests, 0, 0] and c["stack"].tolist() == [0, 0, 0]
+
+
+@pytest.mark.parametrize("name", ["wide_by_one", "mixed_spine"])
+def test_walk_counters_equal_the_closed_form(name):
+    """The counting form's visited set does not depend on the order: a node is entered iff it and every ancestor overlap the
+    box, so node_visits = 1 + 2 (branches entered), leaf_visits = the leaves entered, triangle_tests = their triangles --
+    computed here node by node over all boxes at once, with no stack and no order.  The greatest stack depth any box reaches
+    is the shape's deepest (overlap_shape_cases.deepest_stack), reached by the root's own box."""
+    import overlap_shape_cases as SH
+    import tree_shapes
+    tree, vd = tree_shapes.build(name)
+    corners = vd[tree.triangle_vertices][:, :, :3]
+    boxes = SH.shape_boxes(tree, corners, tree.box, seed=3)
+    lo, hi = OR.lo_hi(boxes)
+    entered = np.zeros((tree.node_count, len(boxes)), bool)
+    for k in range(tree.node_count):
+        nb = tree.box[k]
+        inside = ~((nb[3:] < lo) | (nb[:3] > hi)).any(1)
+        entered[k] = inside & OR.walked(boxes) & (entered[tree.parent[k]] if k else True)
+    branch = tree.negative >= 0
+    c = OR.walk_counters(tree, tree.box, corners, boxes)
+    assert np.array_equal(c["node_visits"], np.where(OR.walked(boxes), 1 + 2 * entered[branch].sum(0), 0))
+    assert np.array_equal(c["leaf_visits"], entered[~branch].sum(0))
+    assert np.array_equal(c["triangle_tests"], (entered[~branch] * tree.triangles[~branch][:, None]).sum(0))
+    assert c["leaf_visits"].sum() > 10 * len(boxes) and (c["node_visits"] == 1).sum() > 20
+    whole = np.nonzero((boxes["lo"] == tree.box[0, :3]).all(1) & (boxes["hi"] == tree.box[0, 3:]).all(1))[0]
+    assert len(whole) == 1 and c["stack"].max() == c["stack"][whole[0]] == SH.deepest_stack(tree)
+    assert c["node_visits"][whole[0]] == tree.node_count
+    # ANY never does more than the counting form, and does less wherever something touches early
+    member = OR.overlaps(corners.reshape(-1), boxes)
+    a = OR.walk_counters(tree, tree.box, corners, boxes, any_only=True, member=member)
+    for key in OR.COUNTERS:
+        assert (a[key] <= c[key]).all()
+    none = ~member.any(1)
+    assert all(np.array_equal(a[key][none], c[key][none]) for key in OR.COUNTERS) and a["triangle_tests"].sum() < c["triangle_tests"].sum() / 10
