@@ -1,7 +1,8 @@
 // client_internal.h -- the host-side scaffolding that the client libraries of libshray_hip.so (query/, refit/, instance/,
-// point/, sdf/, winding/, multihit/, near/, instance_multihit/) share: an owning device allocation, the device switch, the
+// point/, sdf/, winding/, multihit/, near/, overlap/, instance_multihit/) share: an owning device allocation, the device switch, the
 // launch check and the grid of a launch, the split of a large launch, the blocking form of a query, the upload of a tree's
-// height order (tree_order.h) and the bookkeeping of what a library derives from a scene's geometry (DerivedState).
+// height order (tree_order.h) and the bookkeeping of what a library derives from a scene's geometry (DerivedState).  What the
+// counted, first-K queries share on top of it (multihit/, instance_multihit/, near/, overlap/) is point/first_k_query.h.
 // Host-only, internal to the libraries; not part of the C ABI.
 #pragma once
 

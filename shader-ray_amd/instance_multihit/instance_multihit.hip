@@ -15,6 +15,8 @@
 
 #include "all_hits_walk.h"
 #include "client_internal.h"
+#include "first_k_query.h"
+#include "multihit_host.h"
 #include "packed_walk.h"
 #include "shader_ray_instance_multihit.h"
 #include "top_level.h"
@@ -23,8 +25,6 @@
 using namespace shray;
 
 namespace {
-
-constexpr uint64_t kRaysPerLaunch = 1ull << 24;   // the grid's threads stay far below 2^32
 
 struct SetWork {
     const float4 *rays;    // 2 float4 per ray, world space
@@ -111,35 +111,7 @@ __global__ void __launch_bounds__(kBlock) instance_all_hits_kernel(SetWork w, co
         add_counters(rc, w.counters);   // (every lane of the wave is here)
 }
 
-int check_params(const shray_multihit_params *mp)
-{
-    if (!mp)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "multihit params are NULL");
-    if (mp->struct_size != sizeof(shray_multihit_params))
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "shray_multihit_params.struct_size is %u, this library expects %zu", mp->struct_size,
-                    sizeof(shray_multihit_params));
-    if (mp->max_hits < 0 || mp->max_hits > SHRAY_MULTIHIT_MAX || mp->max_leaf_tests < 0 || mp->max_leaf_tests > (1 << 24) || mp->reserved != 0)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "multihit params out of range (max_hits %d of 0 .. %d, max_leaf_tests %d, reserved %d)",
-                    mp->max_hits, (int)SHRAY_MULTIHIT_MAX, mp->max_leaf_tests, mp->reserved);
-    return SHRAY_OK;
-}
-
-// the checks every form makes before it touches a set or a device
-int check_query(shray_instance_set *set, const shray_multihit_params *mp, const void *rays, int64_t count, const void *hits, const void *counts)
-{
-    const int rc = check_params(mp);
-    if (rc)
-        return rc;
-    if (count < 0)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "negative ray count %lld", (long long)count);
-    if (!set || !rays)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "set or rays is NULL");
-    if (mp->max_hits > 0 && !hits)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "hits is NULL with max_hits %d", mp->max_hits);
-    if (mp->max_hits == 0 && !counts)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "nothing is asked for: max_hits is 0 and counts is NULL");
-    return SHRAY_OK;
-}
+constexpr Nouns kNouns = {"ray", "rays", "set", "hits", "max_hits", "instanced all-hits ray query"};
 
 // the set's arrays on its device, and the height of its tallest member tree (each member's read back once per scene)
 int enter_set(shray_instance_set *set, ShrayInstanceSetDevice *d, int *height)
@@ -161,24 +133,10 @@ int enter_set(shray_instance_set *set, ShrayInstanceSetDevice *d, int *height)
     return SHRAY_OK;
 }
 
-template <int SLOTS>
-void launch_form(dim3 grid, size_t lds, hipStream_t stream, const ShrayInstanceSetDevice &d, const SetWork &w)
-{
-    const TopNode *nodes = static_cast<const TopNode *>(d.nodes);
-    const float4 *records = static_cast<const float4 *>(d.records);
-    const SceneView *views = static_cast<const SceneView *>(d.views);
-    if (w.counters)
-        hipLaunchKernelGGL((instance_all_hits_kernel<SLOTS, false, true>), grid, dim3(kBlock), lds, stream, w, nodes, records, views);
-    else if (w.counts || w.k == 0)
-        hipLaunchKernelGGL((instance_all_hits_kernel<SLOTS, false, false>), grid, dim3(kBlock), lds, stream, w, nodes, records, views);
-    else
-        hipLaunchKernelGGL((instance_all_hits_kernel<SLOTS, true, false>), grid, dim3(kBlock), lds, stream, w, nodes, records, views);
-}
-
 int trace_device(shray_instance_set *set, const shray_multihit_params *mp, const shray_ray *d_rays, int64_t count, shray_hit *d_hits,
                  int32_t *d_instances, int32_t *d_counts, hipStream_t stream, DeviceCounters *d_counters)
 {
-    int rc = check_query(set, mp, d_rays, count, d_hits, d_counts);
+    int rc = check_query(kNouns, set, mp, d_rays, count, d_hits, d_counts);
     if (rc)
         return rc;
     const int k = mp->max_hits;
@@ -192,29 +150,25 @@ int trace_device(shray_instance_set *set, const shray_multihit_params *mp, const
         return rc;
     // the form that keeps its K best in the ray's output slots keeps the instance half of the keys there too: without an
     // instance buffer of the caller's, in scratch that is taken and given back in stream order
-    const bool in_memory = k > 8;
     int32_t *scratch = nullptr;
-    if (in_memory && !d_instances) {
+    if (kept_in_memory(k) && !d_instances) {
         HIP_TRY(hipMallocAsync((void **)&scratch, (size_t)count * (size_t)k * sizeof(int32_t), stream));
         d_instances = scratch;
     }
-    const int levels = height > 0 ? height : 1;
+    const int levels = (int)stack_levels(height);
     SetWork w{(const float4 *)d_rays, k > 0 ? (float4 *)d_hits : nullptr, k > 0 ? d_instances : nullptr, d_counts, (uint64_t)count, 0, k,
               mp->max_leaf_tests, levels, d_counters};
     const size_t lds = ((size_t)kBlock * (size_t)levels + kTopStack) * sizeof(uint32_t);
-    rc = for_each_launch(((uint64_t)count + kBlock - 1) / kBlock, kRaysPerLaunch / kBlock, [&](uint64_t first, dim3 grid) {
-        w.first = first * kBlock;
-        if (k == 0 || in_memory)
-            launch_form<kSlotsInMemory>(grid, lds, stream, d, w);
-        else if (k == 1)
-            launch_form<1>(grid, lds, stream, d, w);
-        else if (k == 2)
-            launch_form<2>(grid, lds, stream, d, w);
-        else if (k <= 4)
-            launch_form<4>(grid, lds, stream, d, w);
-        else
-            launch_form<8>(grid, lds, stream, d, w);
-        return launched("instanced all-hits ray query");
+    const TopNode *nodes = static_cast<const TopNode *>(d.nodes);
+    const float4 *records = static_cast<const float4 *>(d.records);
+    const SceneView *views = static_cast<const SceneView *>(d.views);
+    rc = first_k_launches(kNouns, w, count, [&](dim3 grid) {
+        with_slots(k, [&](auto slots) {
+            with_form(form_for(d_counters, d_counts, k), [&](auto prune, auto tally) {
+                hipLaunchKernelGGL((instance_all_hits_kernel<decltype(slots)::value, decltype(prune)::value, decltype(tally)::value>), grid,
+                                   dim3(kBlock), lds, stream, w, nodes, records, views);
+            });
+        });
     });
     if (scratch) {
         const hipError_t e = hipFreeAsync(scratch, stream);
@@ -228,32 +182,21 @@ int trace_device(shray_instance_set *set, const shray_multihit_params *mp, const
 int trace_host(shray_instance_set *set, const shray_multihit_params *mp, const shray_ray *rays, int64_t count, shray_hit *hits,
                int32_t *instances, int32_t *counts, shray_counters *out)
 {
-    int rc = check_query(set, mp, rays, count, hits, counts);
-    if (rc)
+    if (const int rc = check_query(kNouns, set, mp, rays, count, hits, counts))
         return rc;
-    if (out) {
-        memset(out, 0, sizeof(*out));
-        out->samples = (uint64_t)count;
-    }
-    if (count == 0)
-        return SHRAY_OK;
-    ShrayInstanceSetDevice d;
-    int height = 0;
-    if ((rc = enter_set(set, &d, &height)))   // (the errors of a set come before any allocation)
-        return rc;
-    const size_t n = (size_t)count, k = (size_t)mp->max_hits;
-    return run_blocking({{rays, n * sizeof(shray_ray)}},
-                        {{hits, n * k * sizeof(shray_hit)}, {instances, instances ? n * k * sizeof(int32_t) : 0}, {counts, counts ? n * sizeof(int32_t) : 0}},
-                        out, [&](DeviceBuffer *d_rays, DeviceBuffer *d_out, DeviceCounters *shards) {
-                            return trace_device(set, mp, d_rays->as<const shray_ray>(), count, d_out[0].as<shray_hit>(),
-                                                d_out[1].as<int32_t>(), d_out[2].as<int32_t>(), nullptr, shards);
-                        });
+    return first_k_blocking(
+        {rays, sizeof(shray_ray), hits, sizeof(shray_hit), instances, counts}, count, mp->max_hits, out,
+        [&] {
+            ShrayInstanceSetDevice d;
+            int height = 0;
+            return enter_set(set, &d, &height);
+        },
+        [&](void *d_rays, void *d_hits, int32_t *d_instances, int32_t *d_counts, DeviceCounters *shards) {
+            return trace_device(set, mp, (const shray_ray *)d_rays, count, (shray_hit *)d_hits, d_instances, d_counts, nullptr, shards);
+        });
 }
 
 }   // namespace
-
-static_assert(sizeof(shray_multihit_params) == 16, "shray_multihit_params is 16 bytes");
-static_assert(sizeof(shray_ray) == 32 && sizeof(shray_hit) == 16, "the ray query's records");
 
 extern "C" {
 
@@ -272,9 +215,8 @@ int shray_trace_instances_all_hits(shray_instance_set *set, const shray_multihit
 int shray_trace_instances_all_hits_counters(shray_instance_set *set, const shray_multihit_params *mp, const shray_ray *rays,
                                             int64_t count, shray_hit *hits, int32_t *instances, int32_t *counts, shray_counters *out)
 {
-    if (!out)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "counters is NULL");
-    return trace_host(set, mp, rays, count, hits, instances, counts, out);
+    const int rc = check_counters(out);
+    return rc ? rc : trace_host(set, mp, rays, count, hits, instances, counts, out);
 }
 
 }   // extern "C"

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "exact_div.h"
+#include "first_k_query.h"
 #include "packed_walk.h"
 #include "shader_ray_multihit.h"
 #include "trace_common.h"
@@ -20,7 +21,6 @@ namespace {
 using namespace shray;
 
 constexpr float kDetEps = 0.0000001f;             // fs:311
-constexpr int kSlotsInMemory = 0;                 // SLOTS of the instance that keeps its K best in the ray's output slots
 
 // the key of the header: t as a float comparison, then the triangle index
 __device__ __forceinline__ bool before(float t, int tri, float slot_t, int slot_tri)

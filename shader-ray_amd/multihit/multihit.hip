@@ -17,6 +17,8 @@
 
 #include "all_hits_walk.h"
 #include "client_internal.h"
+#include "first_k_query.h"
+#include "multihit_host.h"
 #include "packed_walk.h"
 #include "shader_ray_multihit.h"
 #include "trace_common.h"
@@ -24,8 +26,6 @@
 using namespace shray;
 
 namespace {
-
-constexpr uint64_t kRaysPerLaunch = 1ull << 24;   // the grid's threads stay far below 2^32
 
 struct MultiWork {
     const float4 *rays;   // 2 float4 per ray
@@ -69,51 +69,12 @@ __global__ void __launch_bounds__(kBlock) all_hits_kernel(SceneView sc, MultiWor
         add_counters(rc, w.counters);   // (every lane of the wave is here)
 }
 
-int check_params(const shray_multihit_params *mp)
-{
-    if (!mp)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "multihit params are NULL");
-    if (mp->struct_size != sizeof(shray_multihit_params))
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "shray_multihit_params.struct_size is %u, this library expects %zu", mp->struct_size,
-                    sizeof(shray_multihit_params));
-    if (mp->max_hits < 0 || mp->max_hits > SHRAY_MULTIHIT_MAX || mp->max_leaf_tests < 0 || mp->max_leaf_tests > (1 << 24) || mp->reserved != 0)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "multihit params out of range (max_hits %d of 0 .. %d, max_leaf_tests %d, reserved %d)",
-                    mp->max_hits, (int)SHRAY_MULTIHIT_MAX, mp->max_leaf_tests, mp->reserved);
-    return SHRAY_OK;
-}
-
-// the checks every form makes before it touches a scene or a device
-int check_query(shray_scene *scene, const shray_multihit_params *mp, const void *rays, int64_t count, const void *hits, const void *counts)
-{
-    const int rc = check_params(mp);
-    if (rc)
-        return rc;
-    if (count < 0)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "negative ray count %lld", (long long)count);
-    if (!scene || !rays)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene or rays is NULL");
-    if (mp->max_hits > 0 && !hits)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "hits is NULL with max_hits %d", mp->max_hits);
-    if (mp->max_hits == 0 && !counts)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "nothing is asked for: max_hits is 0 and counts is NULL");
-    return SHRAY_OK;
-}
-
-template <int SLOTS>
-void launch_form(dim3 grid, size_t entries, hipStream_t stream, const SceneView &view, const MultiWork &w)
-{
-    if (w.counters)
-        hipLaunchKernelGGL((all_hits_kernel<SLOTS, false, true>), grid, dim3(kBlock), entries * sizeof(uint32_t), stream, view, w);
-    else if (w.counts || w.k == 0)
-        hipLaunchKernelGGL((all_hits_kernel<SLOTS, false, false>), grid, dim3(kBlock), entries * sizeof(uint32_t), stream, view, w);
-    else
-        hipLaunchKernelGGL((all_hits_kernel<SLOTS, true, false>), grid, dim3(kBlock), entries * sizeof(uint32_t), stream, view, w);
-}
+constexpr Nouns kNouns = {"ray", "rays", "scene", "hits", "max_hits", "all-hits ray query"};
 
 int trace_device(shray_scene *scene, const shray_multihit_params *mp, const shray_ray *d_rays, int64_t count, shray_hit *d_hits,
                  int32_t *d_counts, hipStream_t stream, DeviceCounters *d_counters)
 {
-    int rc = check_query(scene, mp, d_rays, count, d_hits, d_counts);
+    int rc = check_query(kNouns, scene, mp, d_rays, count, d_hits, d_counts);
     if (rc)
         return rc;
     const int k = mp->max_hits;
@@ -126,20 +87,14 @@ int trace_device(shray_scene *scene, const shray_multihit_params *mp, const shra
     if ((rc = enter_walkable_scene(scene, &q, &height)))
         return rc;
     MultiWork w{(const float4 *)d_rays, k > 0 ? (float4 *)d_hits : nullptr, d_counts, (uint64_t)count, 0, k, mp->max_leaf_tests, d_counters};
-    const size_t entries = (size_t)kBlock * (size_t)(height > 0 ? height : 1);
-    return for_each_launch(((uint64_t)count + kBlock - 1) / kBlock, kRaysPerLaunch / kBlock, [&](uint64_t first, dim3 grid) {
-        w.first = first * kBlock;
-        if (k == 0 || k > 8)
-            launch_form<kSlotsInMemory>(grid, entries, stream, q.view, w);
-        else if (k == 1)
-            launch_form<1>(grid, entries, stream, q.view, w);
-        else if (k == 2)
-            launch_form<2>(grid, entries, stream, q.view, w);
-        else if (k <= 4)
-            launch_form<4>(grid, entries, stream, q.view, w);
-        else
-            launch_form<8>(grid, entries, stream, q.view, w);
-        return launched("all-hits ray query");
+    const size_t lds = (size_t)kBlock * stack_levels(height) * sizeof(uint32_t);
+    return first_k_launches(kNouns, w, count, [&](dim3 grid) {
+        with_slots(k, [&](auto slots) {
+            with_form(form_for(d_counters, d_counts, k), [&](auto prune, auto tally) {
+                hipLaunchKernelGGL((all_hits_kernel<decltype(slots)::value, decltype(prune)::value, decltype(tally)::value>), grid, dim3(kBlock),
+                                   lds, stream, q.view, w);
+            });
+        });
     });
 }
 
@@ -147,31 +102,21 @@ int trace_device(shray_scene *scene, const shray_multihit_params *mp, const shra
 int trace_host(shray_scene *scene, const shray_multihit_params *mp, const shray_ray *rays, int64_t count, shray_hit *hits,
                int32_t *counts, shray_counters *out)
 {
-    int rc = check_query(scene, mp, rays, count, hits, counts);
-    if (rc)
+    if (const int rc = check_query(kNouns, scene, mp, rays, count, hits, counts))
         return rc;
-    if (out) {
-        memset(out, 0, sizeof(*out));
-        out->samples = (uint64_t)count;
-    }
-    if (count == 0)
-        return SHRAY_OK;
-    ShrayQueryScene q;
-    int height = 0;
-    if ((rc = enter_walkable_scene(scene, &q, &height)))   // (the errors of a scene come before any allocation)
-        return rc;
-    const size_t n = (size_t)count, k = (size_t)mp->max_hits;
-    return run_blocking({{rays, n * sizeof(shray_ray)}}, {{hits, n * k * sizeof(shray_hit)}, {counts, counts ? n * sizeof(int32_t) : 0}}, out,
-                        [&](DeviceBuffer *d_rays, DeviceBuffer *d_out, DeviceCounters *shards) {
-                            return trace_device(scene, mp, d_rays->as<const shray_ray>(), count, d_out[0].as<shray_hit>(),
-                                                d_out[1].as<int32_t>(), nullptr, shards);
-                        });
+    return first_k_blocking(
+        {rays, sizeof(shray_ray), hits, sizeof(shray_hit), nullptr, counts}, count, mp->max_hits, out,
+        [&] {
+            ShrayQueryScene q;
+            int height = 0;
+            return enter_walkable_scene(scene, &q, &height);
+        },
+        [&](void *d_rays, void *d_hits, int32_t *, int32_t *d_counts, DeviceCounters *shards) {
+            return trace_device(scene, mp, (const shray_ray *)d_rays, count, (shray_hit *)d_hits, d_counts, nullptr, shards);
+        });
 }
 
 }   // namespace
-
-static_assert(sizeof(shray_multihit_params) == 16, "shray_multihit_params is 16 bytes");
-static_assert(sizeof(shray_ray) == 32 && sizeof(shray_hit) == 16, "the ray query's records");
 
 extern "C" {
 
@@ -200,9 +145,8 @@ int shray_trace_all_hits(shray_scene *scene, const shray_multihit_params *mp, co
 int shray_trace_all_hits_counters(shray_scene *scene, const shray_multihit_params *mp, const shray_ray *rays, int64_t count,
                                   shray_hit *hits, int32_t *counts, shray_counters *out)
 {
-    if (!out)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "counters is NULL");
-    return trace_host(scene, mp, rays, count, hits, counts, out);
+    const int rc = check_counters(out);
+    return rc ? rc : trace_host(scene, mp, rays, count, hits, counts, out);
 }
 
 }   // extern "C"

@@ -20,6 +20,7 @@
 
 #include "client_internal.h"
 #include "closest_on_triangle.h"
+#include "first_k_query.h"
 #include "packed_walk.h"
 #include "shader_ray_near.h"
 
@@ -33,7 +34,6 @@ using namespace shray;
 
 namespace {
 
-constexpr int kSlotsInMemory = 0;   // SLOTS of the instance that keeps its K best in the point's output slots
 #if SHRAY_NEAR_NAME_STACK
 using StackEntry = uint32_t;
 #else
@@ -216,6 +216,8 @@ __global__ void __launch_bounds__(kBlock) near_kernel(SceneView sc, NearWork w)
     }
 }
 
+constexpr Nouns kNouns = {"point", "points", "scene", "out", "max_near", "within-radius query"};
+
 int check_params(const shray_near_params *np)
 {
     if (!np)
@@ -233,28 +235,7 @@ int check_params(const shray_near_params *np)
 int check_query(shray_scene *scene, const shray_near_params *np, const void *points, int64_t count, const void *out, const void *counts)
 {
     const int rc = check_params(np);
-    if (rc)
-        return rc;
-    if (count < 0)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "negative point count %lld", (long long)count);
-    if (!scene || !points)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene or points is NULL");
-    if (np->max_near > 0 && !out)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "out is NULL with max_near %d", np->max_near);
-    if (np->max_near == 0 && !counts)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "nothing is asked for: max_near is 0 and counts is NULL");
-    return SHRAY_OK;
-}
-
-template <int SLOTS>
-void launch_form(dim3 grid, size_t lds, hipStream_t stream, const SceneView &view, const NearWork &w)
-{
-    if (w.counters)
-        hipLaunchKernelGGL((near_kernel<SLOTS, false, true>), grid, dim3(kBlock), lds, stream, view, w);
-    else if (w.counts || w.k == 0)
-        hipLaunchKernelGGL((near_kernel<SLOTS, false, false>), grid, dim3(kBlock), lds, stream, view, w);
-    else
-        hipLaunchKernelGGL((near_kernel<SLOTS, true, false>), grid, dim3(kBlock), lds, stream, view, w);
+    return rc ? rc : check_first_k(kNouns, scene, points, count, np->max_near, out, counts);
 }
 
 int near_device(shray_scene *scene, const shray_near_params *np, const shray_point *d_points, int64_t count, shray_closest *d_out,
@@ -273,20 +254,14 @@ int near_device(shray_scene *scene, const shray_near_params *np, const shray_poi
     if ((rc = enter_walkable_scene(scene, &q, &height)))
         return rc;
     NearWork w{(const float4 *)d_points, k > 0 ? (float4 *)d_out : nullptr, d_counts, (uint64_t)count, 0, k, d_counters};
-    const size_t lds = (size_t)kBlock * (size_t)(height > 0 ? height : 1) * sizeof(StackEntry);
-    return for_each_launch(((uint64_t)count + kBlock - 1) / kBlock, kPointsPerLaunch / kBlock, [&](uint64_t first, dim3 grid) {
-        w.first = first * kBlock;
-        if (k == 0 || k > 8)
-            launch_form<kSlotsInMemory>(grid, lds, stream, q.view, w);
-        else if (k == 1)
-            launch_form<1>(grid, lds, stream, q.view, w);
-        else if (k == 2)
-            launch_form<2>(grid, lds, stream, q.view, w);
-        else if (k <= 4)
-            launch_form<4>(grid, lds, stream, q.view, w);
-        else
-            launch_form<8>(grid, lds, stream, q.view, w);
-        return launched("within-radius query");
+    const size_t lds = (size_t)kBlock * stack_levels(height) * sizeof(StackEntry);
+    return first_k_launches(kNouns, w, count, [&](dim3 grid) {
+        with_slots(k, [&](auto slots) {
+            with_form(form_for(d_counters, d_counts, k), [&](auto prune, auto tally) {
+                hipLaunchKernelGGL((near_kernel<decltype(slots)::value, decltype(prune)::value, decltype(tally)::value>), grid, dim3(kBlock), lds,
+                                   stream, q.view, w);
+            });
+        });
     });
 }
 
@@ -294,25 +269,18 @@ int near_device(shray_scene *scene, const shray_near_params *np, const shray_poi
 int near_host(shray_scene *scene, const shray_near_params *np, const shray_point *points, int64_t count, shray_closest *out,
               int32_t *counts, shray_counters *tallies)
 {
-    int rc = check_query(scene, np, points, count, out, counts);
-    if (rc)
+    if (const int rc = check_query(scene, np, points, count, out, counts))
         return rc;
-    if (tallies) {
-        memset(tallies, 0, sizeof(*tallies));
-        tallies->samples = (uint64_t)count;
-    }
-    if (count == 0)
-        return SHRAY_OK;
-    ShrayQueryScene q;
-    int height = 0;
-    if ((rc = enter_walkable_scene(scene, &q, &height)))   // (the errors of a scene come before any allocation)
-        return rc;
-    const size_t n = (size_t)count, k = (size_t)np->max_near;
-    return run_blocking({{points, n * sizeof(shray_point)}}, {{out, n * k * sizeof(shray_closest)}, {counts, counts ? n * sizeof(int32_t) : 0}},
-                        tallies, [&](DeviceBuffer *d_points, DeviceBuffer *d_out, DeviceCounters *shards) {
-                            return near_device(scene, np, d_points->as<const shray_point>(), count, d_out[0].as<shray_closest>(),
-                                               d_out[1].as<int32_t>(), nullptr, shards);
-                        });
+    return first_k_blocking(
+        {points, sizeof(shray_point), out, sizeof(shray_closest), nullptr, counts}, count, np->max_near, tallies,
+        [&] {
+            ShrayQueryScene q;
+            int height = 0;
+            return enter_walkable_scene(scene, &q, &height);
+        },
+        [&](void *d_points, void *d_out, int32_t *, int32_t *d_counts, DeviceCounters *shards) {
+            return near_device(scene, np, (const shray_point *)d_points, count, (shray_closest *)d_out, d_counts, nullptr, shards);
+        });
 }
 
 }   // namespace
@@ -346,9 +314,8 @@ int shray_near_triangles(shray_scene *scene, const shray_near_params *np, const 
 int shray_near_triangles_counters(shray_scene *scene, const shray_near_params *np, const shray_point *points, int64_t count,
                                   shray_closest *out, int32_t *counts, shray_counters *counters)
 {
-    if (!counters)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "counters is NULL");
-    return near_host(scene, np, points, count, out, counts, counters);
+    const int rc = check_counters(counters);
+    return rc ? rc : near_host(scene, np, points, count, out, counts, counters);
 }
 
 }   // extern "C"

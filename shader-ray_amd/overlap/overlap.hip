@@ -16,6 +16,7 @@
 #include <cstring>
 
 #include "client_internal.h"
+#include "first_k_query.h"
 #include "packed_walk.h"
 #include "shader_ray_overlap.h"
 
@@ -23,7 +24,6 @@ using namespace shray;
 
 namespace {
 
-constexpr int kSlotsInMemory = 0;          // SLOTS of the instance that keeps its K smallest in the box's output slots
 constexpr uint32_t kEmpty = 0xffffffffu;   // SHRAY_HIT_MISS as an unsigned index: after every triangle
 
 struct OverlapWork {
@@ -212,6 +212,8 @@ __global__ void __launch_bounds__(kBlock) overlap_kernel(SceneView sc, OverlapWo
     }
 }
 
+constexpr Nouns kNouns = {"box", "boxes", "scene", "out", "max_triangles", "box-overlap query"};
+
 int check_params(const shray_overlap_params *op)
 {
     if (!op)
@@ -231,19 +233,14 @@ int check_query(shray_scene *scene, const shray_overlap_params *op, const void *
     const int rc = check_params(op);
     if (rc)
         return rc;
-    if (count < 0)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "negative box count %lld", (long long)count);
-    if (!scene || !boxes)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene or boxes is NULL");
-    if ((op->flags & SHRAY_OVERLAP_ANY) && (op->max_triangles != 0 || !counts))
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "SHRAY_OVERLAP_ANY needs max_triangles 0 (it is %d) and counts", op->max_triangles);
-    if (op->max_triangles > 0 && !out)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "out is NULL with max_triangles %d", op->max_triangles);
-    if (op->max_triangles == 0 && !counts)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "nothing is asked for: max_triangles is 0 and counts is NULL");
-    return SHRAY_OK;
+    return check_first_k(kNouns, scene, boxes, count, op->max_triangles, out, counts, [&] {
+        if ((op->flags & SHRAY_OVERLAP_ANY) && (op->max_triangles != 0 || !counts))
+            return fail(SHRAY_ERR_INVALID_ARGUMENT, "SHRAY_OVERLAP_ANY needs max_triangles 0 (it is %d) and counts", op->max_triangles);
+        return (int)SHRAY_OK;
+    });
 }
 
+// (this walk has no form that prunes: the choice is the work counters alone)
 template <int SLOTS>
 void launch_form(dim3 grid, size_t lds, hipStream_t stream, const SceneView &view, const OverlapWork &w)
 {
@@ -270,24 +267,14 @@ int overlap_device(shray_scene *scene, const shray_overlap_params *op, const shr
     if ((rc = enter_walkable_scene(scene, &q, &height)))
         return rc;
     OverlapWork w{(const float4 *)d_boxes, k > 0 ? d_out : nullptr, d_counts, (uint64_t)count, 0, k, d_counters};
-    const size_t lds = (size_t)kBlock * (size_t)(height > 0 ? height : 1) * sizeof(uint32_t);
-    return for_each_launch(((uint64_t)count + kBlock - 1) / kBlock, kPointsPerLaunch / kBlock, [&](uint64_t first, dim3 grid) {
-        w.first = first * kBlock;
+    const size_t lds = (size_t)kBlock * stack_levels(height) * sizeof(uint32_t);
+    return first_k_launches(kNouns, w, count, [&](dim3 grid) {
         if (any && d_counters)
             hipLaunchKernelGGL((overlap_kernel<kSlotsInMemory, true, true>), grid, dim3(kBlock), lds, stream, q.view, w);
         else if (any)
             hipLaunchKernelGGL((overlap_kernel<kSlotsInMemory, true, false>), grid, dim3(kBlock), lds, stream, q.view, w);
-        else if (k == 0 || k > 8)
-            launch_form<kSlotsInMemory>(grid, lds, stream, q.view, w);
-        else if (k == 1)
-            launch_form<1>(grid, lds, stream, q.view, w);
-        else if (k == 2)
-            launch_form<2>(grid, lds, stream, q.view, w);
-        else if (k <= 4)
-            launch_form<4>(grid, lds, stream, q.view, w);
         else
-            launch_form<8>(grid, lds, stream, q.view, w);
-        return launched("box-overlap query");
+            with_slots(k, [&](auto slots) { launch_form<decltype(slots)::value>(grid, lds, stream, q.view, w); });
     });
 }
 
@@ -295,27 +282,20 @@ int overlap_device(shray_scene *scene, const shray_overlap_params *op, const shr
 int overlap_host(shray_scene *scene, const shray_overlap_params *op, const shray_box *boxes, int64_t count, int32_t *out, int32_t *counts,
                  shray_counters *tallies)
 {
-    int rc = check_query(scene, op, boxes, count, out, counts);
-    if (rc)
+    if (const int rc = check_query(scene, op, boxes, count, out, counts))
         return rc;
     if (!aligned(boxes, 16) || (out && !aligned(out, 4)) || (counts && !aligned(counts, 4)))
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "the boxes must be 16-byte aligned, the indices and the counts 4-byte aligned");
-    if (tallies) {
-        memset(tallies, 0, sizeof(*tallies));
-        tallies->samples = (uint64_t)count;
-    }
-    if (count == 0)
-        return SHRAY_OK;
-    ShrayQueryScene q;
-    int height = 0;
-    if ((rc = enter_walkable_scene(scene, &q, &height)))   // (the errors of a scene come before any allocation)
-        return rc;
-    const size_t n = (size_t)count, k = (size_t)op->max_triangles;
-    return run_blocking({{boxes, n * sizeof(shray_box)}}, {{out, n * k * sizeof(int32_t)}, {counts, counts ? n * sizeof(int32_t) : 0}}, tallies,
-                        [&](DeviceBuffer *d_boxes, DeviceBuffer *d_out, DeviceCounters *shards) {
-                            return overlap_device(scene, op, d_boxes->as<const shray_box>(), count, d_out[0].as<int32_t>(),
-                                                  d_out[1].as<int32_t>(), nullptr, shards);
-                        });
+    return first_k_blocking(
+        {boxes, sizeof(shray_box), out, sizeof(int32_t), nullptr, counts}, count, op->max_triangles, tallies,
+        [&] {
+            ShrayQueryScene q;
+            int height = 0;
+            return enter_walkable_scene(scene, &q, &height);
+        },
+        [&](void *d_boxes, void *d_out, int32_t *, int32_t *d_counts, DeviceCounters *shards) {
+            return overlap_device(scene, op, (const shray_box *)d_boxes, count, (int32_t *)d_out, d_counts, nullptr, shards);
+        });
 }
 
 }   // namespace
@@ -350,9 +330,8 @@ int shray_overlap_triangles(shray_scene *scene, const shray_overlap_params *op, 
 int shray_overlap_triangles_counters(shray_scene *scene, const shray_overlap_params *op, const shray_box *boxes, int64_t count,
                                      int32_t *out, int32_t *counts, shray_counters *counters)
 {
-    if (!counters)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "counters is NULL");
-    return overlap_host(scene, op, boxes, count, out, counts, counters);
+    const int rc = check_counters(counters);
+    return rc ? rc : overlap_host(scene, op, boxes, count, out, counts, counters);
 }
 
 }   // extern "C"

@@ -1,6 +1,8 @@
 // packed_walk.h -- what the one-lane-per-item walks over octant copy 7 of the packed tree share (the closest-point walk,
-// point_walk.h, the within-radius walk, near/near.hip, the winding-number walk, winding/winding.hip, and the all-hits ray
-// walk, multihit/multihit.hip): a record's load, the sum over a wave that flushes a walk's work counters, the points of one launch, the readback
+// point_walk.h, the within-radius walk, near/near.hip, the winding-number walk, winding/winding.hip, the box-overlap walk,
+// overlap/overlap.hip, and the all-hits ray walk, multihit/all_hits_walk.h, which multihit/multihit.hip and
+// instance_multihit/instance_multihit.hip run): a record's load, the sum over a wave that flushes a walk's work counters, the
+// items (points, rays, boxes) of one launch, the readback
 // of copy 7 into csrc/tree_order.h's height order, the tree's height and where it is kept per scene, and the refusals of a
 // scene before anything is launched.  Internal to the libraries; no kernel is defined here.
 #pragma once
@@ -25,7 +27,7 @@ using namespace shray;
 
 constexpr int kBlock = 64;    // one wave per workgroup: a lane's stack column is its own
 constexpr int kOctant = 7;    // the copy whose entry planes are boxmin and exit planes boxmax
-constexpr uint64_t kPointsPerLaunch = 1ull << 24;   // the grid's threads stay far below 2^32
+constexpr uint64_t kPointsPerLaunch = 1ull << 24;   // items (a lane each) of one launch: the grid's threads stay far below 2^32
 
 struct Box {
     float lo[3], hi[3];

@@ -5,6 +5,7 @@ kernels behind the C ABI.  There is no CPU fallback."""
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -338,38 +339,9 @@ class Scene:
         first `max_hits` (the same records); max_hits = 0 returns None for the hits.  counters=True (host rays only) also
         returns the counters of the walk that skips nothing (shray_trace_all_hits_counters)."""
         lib = N.load_multihit()
-        mp = multihit_params(max_hits, max_leaf_tests)
-        if max_hits == 0 and not counts:
-            raise ValueError("nothing is asked for: max_hits is 0 and counts is False")
-        rays = _host_if_cpu(rays)
-        if _is_torch(rays):
-            import torch
-            if counters:
-                raise ValueError("counters are counted on the host path: pass host rays")
-            if rays.device.index != self.device_index():
-                raise ValueError(f"rays are on {rays.device}, the scene on cuda:{self.device_index()}")
-            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-                raise ValueError("a GPU ray tensor must be float32 [n, 8] (the shray_ray layout)")
-            r = rays.contiguous()
-            hits = torch.empty((len(r), max_hits, 4), dtype=torch.int32, device=r.device) if max_hits > 0 else None
-            cnt = torch.empty(len(r), dtype=torch.int32, device=r.device) if counts else None
-            stream = torch.cuda.current_stream(r.device)
-            r.record_stream(stream)   # (the query reads it after this call returns)
-            N.check(lib.shray_trace_all_hits_device(self._handle, C.byref(mp), C.c_void_p(r.data_ptr()), len(r),
-                                                    C.c_void_p(hits.data_ptr() if hits is not None else None),
-                                                    C.c_void_p(cnt.data_ptr() if counts else None), C.c_void_p(stream.cuda_stream)))
-            return hits, cnt
-        rays = _host_rays(rays)
-        hits = np.empty((len(rays), max_hits), HIT_DTYPE) if max_hits > 0 else None   # (the library refuses a negative one)
-        cnt = np.empty(len(rays), np.int32) if counts else None
-        args = (self._handle, C.byref(mp), rays.ctypes.data_as(C.c_void_p), len(rays),
-                hits.ctypes.data_as(C.c_void_p) if hits is not None else None, cnt.ctypes.data_as(C.c_void_p) if counts else None)
-        if counters:
-            c = N.Counters()
-            N.check(lib.shray_trace_all_hits_counters(*args, C.byref(c)))
-            return hits, cnt, c.as_dict()
-        N.check(lib.shray_trace_all_hits(*args))
-        return hits, cnt
+        return _first_k(self._handle, (lib.shray_trace_all_hits_device, lib.shray_trace_all_hits, lib.shray_trace_all_hits_counters),
+                        multihit_params(max_hits, max_leaf_tests), max_hits, "max_hits", rays, "rays",
+                        lambda r: _device_rays(r, self.device_index(), "the scene"), _host_rays, HIT_DTYPE, (4,), False, counts, counters)
 
     def trace_all_hits_into(self, rays_ptr: int, count: int, hits_ptr: int, counts_ptr: int = 0, max_hits: int = 8, stream_ptr: int = 0,
                             max_leaf_tests: int = 10):
@@ -397,34 +369,9 @@ class Scene:
         records); max_near = 0 returns None for the records.  counters=True (host points only) also returns the counters of
         the walk that prunes only by max_dist2 (shray_near_triangles_counters)."""
         lib = N.load_near()
-        np_ = near_params(max_near)
-        if max_near == 0 and not counts:
-            raise ValueError("nothing is asked for: max_near is 0 and counts is False")
-        points = _host_if_cpu(points)
-        if _is_torch(points):
-            import torch
-            if counters:
-                raise ValueError("counters are counted on the host path: pass host points")
-            pts = self._device_points(points)
-            out = torch.empty((len(pts), max_near, 8), dtype=torch.int32, device=pts.device) if max_near > 0 else None
-            cnt = torch.empty(len(pts), dtype=torch.int32, device=pts.device) if counts else None
-            stream = torch.cuda.current_stream(pts.device)
-            pts.record_stream(stream)   # (the query reads it after this call returns)
-            N.check(lib.shray_near_triangles_device(self._handle, C.byref(np_), C.c_void_p(pts.data_ptr()), len(pts),
-                                                    C.c_void_p(out.data_ptr() if out is not None else None),
-                                                    C.c_void_p(cnt.data_ptr() if counts else None), C.c_void_p(stream.cuda_stream)))
-            return out, cnt
-        pts = _host_points(points)
-        out = np.empty((len(pts), max_near), CLOSEST_DTYPE) if max_near > 0 else None   # (the library refuses a negative one)
-        cnt = np.empty(len(pts), np.int32) if counts else None
-        args = (self._handle, C.byref(np_), pts.ctypes.data_as(C.c_void_p), len(pts),
-                out.ctypes.data_as(C.c_void_p) if out is not None else None, cnt.ctypes.data_as(C.c_void_p) if counts else None)
-        if counters:
-            c = N.Counters()
-            N.check(lib.shray_near_triangles_counters(*args, C.byref(c)))
-            return out, cnt, c.as_dict()
-        N.check(lib.shray_near_triangles(*args))
-        return out, cnt
+        return _first_k(self._handle, (lib.shray_near_triangles_device, lib.shray_near_triangles, lib.shray_near_triangles_counters),
+                        near_params(max_near), max_near, "max_near", points, "points", self._device_points, _host_points, CLOSEST_DTYPE, (8,),
+                        False, counts, counters)
 
     def triangles_within_into(self, points_ptr: int, count: int, out_ptr: int, counts_ptr: int = 0, max_near: int = 8, stream_ptr: int = 0):
         """Asynchronous within-radius queries on device memory of the scene's device (shray_near_triangles_device): `count`
@@ -450,35 +397,10 @@ class Scene:
         the indices.  any_only=True (with max_triangles = 0) sets SHRAY_OVERLAP_ANY: the count is 1 or 0 and the walk stops at
         the first touching triangle.  counters=True (host boxes only) also returns the walk's counters
         (shray_overlap_triangles_counters)."""
-        if max_triangles == 0 and not counts:
-            raise ValueError("nothing is asked for: max_triangles is 0 and counts is False")
         lib = N.load_overlap()
-        op = overlap_params(max_triangles, any_only)
-        boxes = _host_if_cpu(boxes)
-        if _is_torch(boxes):
-            import torch
-            if counters:
-                raise ValueError("counters are counted on the host path: pass host boxes")
-            bx = self._device_boxes(boxes)
-            out = torch.empty((len(bx), max_triangles), dtype=torch.int32, device=bx.device) if max_triangles > 0 else None
-            cnt = torch.empty(len(bx), dtype=torch.int32, device=bx.device) if counts else None
-            stream = torch.cuda.current_stream(bx.device)
-            bx.record_stream(stream)   # (the query reads it after this call returns)
-            N.check(lib.shray_overlap_triangles_device(self._handle, C.byref(op), C.c_void_p(bx.data_ptr()), len(bx),
-                                                       C.c_void_p(out.data_ptr() if out is not None else None),
-                                                       C.c_void_p(cnt.data_ptr() if counts else None), C.c_void_p(stream.cuda_stream)))
-            return out, cnt
-        bx = _host_boxes(boxes)
-        out = np.empty((len(bx), max_triangles), np.int32) if max_triangles > 0 else None   # (the library refuses a negative one)
-        cnt = np.empty(len(bx), np.int32) if counts else None
-        args = (self._handle, C.byref(op), bx.ctypes.data_as(C.c_void_p), len(bx),
-                out.ctypes.data_as(C.c_void_p) if out is not None else None, cnt.ctypes.data_as(C.c_void_p) if counts else None)
-        if counters:
-            c = N.Counters()
-            N.check(lib.shray_overlap_triangles_counters(*args, C.byref(c)))
-            return out, cnt, c.as_dict()
-        N.check(lib.shray_overlap_triangles(*args))
-        return out, cnt
+        return _first_k(self._handle, (lib.shray_overlap_triangles_device, lib.shray_overlap_triangles, lib.shray_overlap_triangles_counters),
+                        overlap_params(max_triangles, any_only), max_triangles, "max_triangles", boxes, "boxes", self._device_boxes,
+                        _host_boxes, np.int32, (), False, counts, counters)
 
     def _device_boxes(self, boxes):
         """a float32 [n, 6] / [n, 8] GPU tensor on the scene's device as a contiguous [n, 8] shray_box tensor"""
@@ -624,6 +546,54 @@ def _is_torch(a) -> bool:
 def _host_if_cpu(a):
     """a torch tensor in host memory as a numpy array (the host path takes it); anything else as it is"""
     return a.detach().numpy() if _is_torch(a) and not a.is_cuda else a
+
+
+def _device_rays(rays, device_index: int, owner: str):
+    """a float32 [n, 8] GPU tensor on the device of `owner` ("the scene", "the set") as a contiguous shray_ray tensor"""
+    import torch
+    if rays.device.index != device_index:
+        raise ValueError(f"rays are on {rays.device}, {owner} on cuda:{device_index}")
+    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+        raise ValueError("a GPU ray tensor must be float32 [n, 8] (the shray_ray layout)")
+    return rays.contiguous()
+
+
+def _first_k(handle, functions, params, k: int, k_name: str, items, kind: str, on_device, on_host, record_dtype, trailing, second: bool,
+             counts: bool, counters: bool):
+    """The counted first-K queries (all-hits rays, their instanced form, within-radius, box-overlap): per item a count and
+    its first `k` records.  `functions`: the library's device form, blocking form and blocking form with counters, called with
+    (`handle`, `params`, items, n, records[, second], counts, ...).  `items` (`kind`: "rays", "points", "boxes"): a GPU tensor
+    takes the device path on the current torch stream, through `on_device` (which refuses another device or layout), anything
+    else the blocking path, through `on_host`.  The records are an int32 [n, k, *trailing] tensor or a `record_dtype` [n, k]
+    array, None when `k` is 0; with `second` an int32 [n, k] output follows them (the instances); the counts are int32 [n],
+    None unless `counts`.  Returns (records[, second], counts[, counters])."""
+    device_form, host_form, counters_form = functions
+    if k == 0 and not counts:
+        raise ValueError(f"nothing is asked for: {k_name} is 0 and counts is False")
+    items = _host_if_cpu(items)
+    if _is_torch(items):
+        import torch
+        if counters:
+            raise ValueError(f"counters are counted on the host path: pass host {kind}")
+        d = on_device(items)
+        new = lambda want, *shape: torch.empty((len(d), *shape), dtype=torch.int32, device=d.device) if want else None
+        outs = [new(k > 0, k, *trailing)] + ([new(k > 0, k)] if second else []) + [new(counts)]
+        stream = torch.cuda.current_stream(d.device)
+        d.record_stream(stream)   # (the query reads it after this call returns)
+        N.check(device_form(handle, C.byref(params), C.c_void_p(d.data_ptr()), len(d),
+                            *(C.c_void_p(o.data_ptr() if o is not None else None) for o in outs), C.c_void_p(stream.cuda_stream)))
+        return tuple(outs)
+    d = on_host(items)
+    new = lambda want, dtype, *shape: np.empty((len(d), *shape), dtype) if want else None   # (the library refuses a negative k)
+    outs = [new(k > 0, record_dtype, k)] + ([new(k > 0, np.int32, k)] if second else []) + [new(counts, np.int32)]
+    args = (handle, C.byref(params), d.ctypes.data_as(C.c_void_p), len(d),
+            *(o.ctypes.data_as(C.c_void_p) if o is not None else None for o in outs))
+    if counters:
+        c = N.Counters()
+        N.check(counters_form(*args, C.byref(c)))
+        return (*outs, c.as_dict())
+    N.check(host_form(*args))
+    return tuple(outs)
 
 
 # a ray buffer / hit array of the query (include/shader_ray_query.h): 32 and 16 bytes per element
@@ -859,109 +829,6 @@ class DeviceWorld:
         N.check(self._hip.shray_device_flat_download(self._flat, C.byref(desc)))
         return desc_arrays(desc)
 
-    def trace_rays(self, rays, **kwargs):
-        """Scene.trace_rays on this scene."""
-        return self.scene.trace_rays(rays, **kwargs)
-
-    def trace_rays_into(self, rays_ptr: int, count: int, hits_ptr: int, stream_ptr: int = 0, **kwargs):
-        """Scene.trace_rays_into on this scene."""
-        return self.scene.trace_rays_into(rays_ptr, count, hits_ptr, stream_ptr, **kwargs)
-
-    def trace_all_hits(self, rays, **kwargs):
-        """Scene.trace_all_hits on this scene."""
-        return self.scene.trace_all_hits(rays, **kwargs)
-
-    def trace_all_hits_into(self, rays_ptr: int, count: int, hits_ptr: int, counts_ptr: int = 0, max_hits: int = 8, stream_ptr: int = 0,
-                            **kwargs):
-        """Scene.trace_all_hits_into on this scene."""
-        return self.scene.trace_all_hits_into(rays_ptr, count, hits_ptr, counts_ptr, max_hits, stream_ptr, **kwargs)
-
-    def crossing_counts(self, rays, **kwargs):
-        """Scene.crossing_counts on this scene."""
-        return self.scene.crossing_counts(rays, **kwargs)
-
-    def closest_points(self, points, **kwargs):
-        """Scene.closest_points on this scene."""
-        return self.scene.closest_points(points, **kwargs)
-
-    def closest_points_into(self, points_ptr: int, count: int, out_ptr: int, stream_ptr: int = 0):
-        """Scene.closest_points_into on this scene."""
-        return self.scene.closest_points_into(points_ptr, count, out_ptr, stream_ptr)
-
-    def triangles_within(self, points, **kwargs):
-        """Scene.triangles_within on this scene."""
-        return self.scene.triangles_within(points, **kwargs)
-
-    def triangles_within_into(self, points_ptr: int, count: int, out_ptr: int, counts_ptr: int = 0, max_near: int = 8, stream_ptr: int = 0):
-        """Scene.triangles_within_into on this scene."""
-        return self.scene.triangles_within_into(points_ptr, count, out_ptr, counts_ptr, max_near, stream_ptr)
-
-    def near_counts(self, points):
-        """Scene.near_counts on this scene."""
-        return self.scene.near_counts(points)
-
-    def triangles_in_boxes(self, boxes, **kwargs):
-        """Scene.triangles_in_boxes on this scene."""
-        return self.scene.triangles_in_boxes(boxes, **kwargs)
-
-    def triangles_in_boxes_into(self, boxes_ptr: int, count: int, out_ptr: int, counts_ptr: int = 0, max_triangles: int = 8,
-                                any_only: bool = False, stream_ptr: int = 0):
-        """Scene.triangles_in_boxes_into on this scene."""
-        return self.scene.triangles_in_boxes_into(boxes_ptr, count, out_ptr, counts_ptr, max_triangles, any_only, stream_ptr)
-
-    def box_counts(self, boxes):
-        """Scene.box_counts on this scene."""
-        return self.scene.box_counts(boxes)
-
-    def boxes_touched(self, boxes):
-        """Scene.boxes_touched on this scene."""
-        return self.scene.boxes_touched(boxes)
-
-    def surface_voxels(self, origin, cell, dims, device=None):
-        """Scene.surface_voxels on this scene."""
-        return self.scene.surface_voxels(origin, cell, dims, device)
-
-    def signed_distance(self, points, **kwargs):
-        """Scene.signed_distance on this scene."""
-        return self.scene.signed_distance(points, **kwargs)
-
-    def signed_distance_into(self, points_ptr: int, count: int, out_ptr: int, closest_ptr: int = 0, stream_ptr: int = 0):
-        """Scene.signed_distance_into on this scene."""
-        return self.scene.signed_distance_into(points_ptr, count, out_ptr, closest_ptr, stream_ptr)
-
-    def surface_info(self) -> dict:
-        """Scene.surface_info on this scene."""
-        return self.scene.surface_info()
-
-    def sign_data(self) -> np.ndarray:
-        """Scene.sign_data on this scene."""
-        return self.scene.sign_data()
-
-    def winding_number(self, points, **kwargs):
-        """Scene.winding_number on this scene."""
-        return self.scene.winding_number(points, **kwargs)
-
-    def winding_number_into(self, points_ptr: int, count: int, out_ptr: int, beta: float = 2.0, stream_ptr: int = 0):
-        """Scene.winding_number_into on this scene."""
-        return self.scene.winding_number_into(points_ptr, count, out_ptr, beta, stream_ptr)
-
-    def winding_signed_distance(self, points, **kwargs):
-        """Scene.winding_signed_distance on this scene."""
-        return self.scene.winding_signed_distance(points, **kwargs)
-
-    def winding_signed_distance_into(self, points_ptr: int, count: int, out_ptr: int, closest_ptr: int = 0, beta: float = 2.0,
-                                     stream_ptr: int = 0):
-        """Scene.winding_signed_distance_into on this scene."""
-        return self.scene.winding_signed_distance_into(points_ptr, count, out_ptr, closest_ptr, beta, stream_ptr)
-
-    def winding_data(self) -> np.ndarray:
-        """Scene.winding_data on this scene."""
-        return self.scene.winding_data()
-
-    def primary_hits(self, params: N.FrameParams, width: int, height: int) -> np.ndarray:
-        """Scene.primary_hits on this scene."""
-        return self.scene.primary_hits(params, width, height)
-
     def refit(self, vertex_data, stream_ptr: int | None = None) -> dict:
         """Refits the scene to moved vertices (Scene.refit): `vertex_data` is [V, 3] or [V, 9] float32 (numpy, or a torch tensor on
         the scene's device), in the numbering of the loaded triangle set (shray_host_triangles); with 9 columns (geometry.h:34-38)
@@ -1013,6 +880,27 @@ class DeviceWorld:
             self.close()
         except Exception:
             pass
+
+
+# the Scene methods a DeviceWorld has as its own: each passes its arguments on to .scene unchanged
+_SCENE_FORWARDS = ("trace_rays", "trace_rays_into", "trace_all_hits", "trace_all_hits_into", "crossing_counts", "closest_points",
+                   "closest_points_into", "triangles_within", "triangles_within_into", "near_counts", "triangles_in_boxes",
+                   "triangles_in_boxes_into", "box_counts", "boxes_touched", "surface_voxels", "signed_distance", "signed_distance_into",
+                   "surface_info", "sign_data", "winding_number", "winding_number_into", "winding_signed_distance",
+                   "winding_signed_distance_into", "winding_data", "primary_hits")
+
+
+def _scene_forward(name: str):
+    @functools.wraps(getattr(Scene, name))
+    def forward(self, *args, **kwargs):
+        return getattr(self.scene, name)(*args, **kwargs)
+    forward.__qualname__ = f"DeviceWorld.{name}"
+    return forward
+
+
+for _name in _SCENE_FORWARDS:
+    setattr(DeviceWorld, _name, _scene_forward(_name))
+del _name
 
 
 class InstanceSet:
@@ -1148,42 +1036,10 @@ class InstanceSet:
         instances.  counters=True (host rays only) also returns the counters of the form that skips nothing, summed over
         a ray's walks."""
         lib = N.load_instance_multihit()
-        mp = multihit_params(max_hits, max_leaf_tests)
-        if max_hits == 0 and not counts:
-            raise ValueError("nothing is asked for: max_hits is 0 and counts is False")
-        rays = _host_if_cpu(rays)
-        if _is_torch(rays):
-            import torch
-            if counters:
-                raise ValueError("counters are counted on the host path: pass host rays")
-            if rays.device.index != self.device:
-                raise ValueError(f"rays are on {rays.device}, the set on cuda:{self.device}")
-            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-                raise ValueError("a GPU ray tensor must be float32 [n, 8] (the shray_ray layout)")
-            r = rays.contiguous()
-            hits = torch.empty((len(r), max_hits, 4), dtype=torch.int32, device=r.device) if max_hits > 0 else None
-            inst = torch.empty((len(r), max_hits), dtype=torch.int32, device=r.device) if max_hits > 0 else None
-            cnt = torch.empty(len(r), dtype=torch.int32, device=r.device) if counts else None
-            stream = torch.cuda.current_stream(r.device)
-            r.record_stream(stream)   # (the query reads it after this call returns)
-            N.check(lib.shray_trace_instances_all_hits_device(
-                self._handle, C.byref(mp), C.c_void_p(r.data_ptr()), len(r), C.c_void_p(hits.data_ptr() if hits is not None else None),
-                C.c_void_p(inst.data_ptr() if inst is not None else None), C.c_void_p(cnt.data_ptr() if counts else None),
-                C.c_void_p(stream.cuda_stream)))
-            return hits, inst, cnt
-        rays = _host_rays(rays)
-        hits = np.empty((len(rays), max_hits), HIT_DTYPE) if max_hits > 0 else None   # (the library refuses a negative one)
-        inst = np.empty((len(rays), max_hits), np.int32) if max_hits > 0 else None
-        cnt = np.empty(len(rays), np.int32) if counts else None
-        args = (self._handle, C.byref(mp), rays.ctypes.data_as(C.c_void_p), len(rays),
-                hits.ctypes.data_as(C.c_void_p) if hits is not None else None,
-                inst.ctypes.data_as(C.c_void_p) if inst is not None else None, cnt.ctypes.data_as(C.c_void_p) if counts else None)
-        if counters:
-            c = N.Counters()
-            N.check(lib.shray_trace_instances_all_hits_counters(*args, C.byref(c)))
-            return hits, inst, cnt, c.as_dict()
-        N.check(lib.shray_trace_instances_all_hits(*args))
-        return hits, inst, cnt
+        return _first_k(self._handle, (lib.shray_trace_instances_all_hits_device, lib.shray_trace_instances_all_hits,
+                                       lib.shray_trace_instances_all_hits_counters),
+                        multihit_params(max_hits, max_leaf_tests), max_hits, "max_hits", rays, "rays",
+                        lambda r: _device_rays(r, self.device, "the set"), _host_rays, HIT_DTYPE, (4,), True, counts, counters)
 
     def trace_all_hits_into(self, rays_ptr: int, count: int, hits_ptr: int, instances_ptr: int = 0, counts_ptr: int = 0,
                             max_hits: int = 8, stream_ptr: int = 0, max_leaf_tests: int = 10):

@@ -41,7 +41,7 @@ def test_one_identity_instance_is_the_all_hits_query(pkg, gpu, name):
     rays = pkg.tracer.make_rays(o, d, tmax)
     s = pkg.tracer.InstanceSet([sc], EYE[None])
     try:
-        for k in (0, 1, 3, 8, 64):
+        for k in (0, 1, 3, 5, 8, 64):
             for with_counts in (True, False):
                 if k == 0 and not with_counts:
                     continue
@@ -91,7 +91,7 @@ def test_a_set_of_two_equals_the_restatement(pkg, gpu):
         per = want[5]
         assert ((per[0] > 0) & (per[1] > 0)).sum() > 100, "the two overlap: many rays cross both"
         d_rays = dev(rays)
-        for k in (0, 1, 2, 4, 8, 64):
+        for k in (0, 1, 2, 4, 5, 8, 64):
             for with_counts in (True, False):
                 if k == 0 and not with_counts:
                     continue

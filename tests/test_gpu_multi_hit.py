@@ -1,5 +1,5 @@
 """All-hits ray queries on the GPU (include/shader_ray_multihit.h) against the restatement (tests/multi_hit_ref.py): every
-byte of every hit record and every count, for K in {0, 1, 3, 8, 64} with and without counts (the walk that skips what cannot
+byte of every hit record and every count, for K in {0, 1, 2, 3, 4, 5, 8, 9, 64} with and without counts (the walk that skips what cannot
 reach the first K against the walk that skips nothing), on the test scenes and the reference test's small meshes with the
 ray query's random rays; the host and device paths, DeviceWorld, a count split over two launches, the counters, a device
 refit followed by the query on the same stream, the refusal of a scene without a packed tree, trace_rays' closest hit
@@ -18,7 +18,7 @@ from test_oracle_kat import chain_scene
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-KS = (0, 1, 3, 8, 64)
+KS = (0, 1, 2, 3, 4, 5, 8, 9, 64)
 SCENES = [("small_trisrc", 30000), ("lobed_528", 30000), ("bunny", 30000), ("quads_mixed", 30000)] + [(m, 20000) for m in M.MESHES]
 _small = {}
 _refs = {}

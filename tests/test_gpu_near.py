@@ -1,6 +1,6 @@
 """Within-radius queries on the GPU (include/shader_ray_near.h) against the restatement (tests/near_ref.py): every byte of every
 record and every count, for the closest-point tests' kinds of point and radius mix plus radii of 5 to 20 % of the extent
-(tests/near_cases.py), K in {0, 1, 2, 3, 4, 8, 9, 64} with and without counts; the pruned form against the counting form and,
+(tests/near_cases.py), K in {0, 1, 2, 3, 4, 5, 8, 9, 64} with and without counts; the pruned form against the counting form and,
 at K = 1, against Scene.closest_points byte for byte; the host and device (torch stream) paths; host-built scenes and
 DeviceWorld; after a device refit on the same stream; the counters; a count split over launches; and the refusals.  No case is
 skipped or tolerated."""
@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 
 F = np.float32
 BAD_TREE = -6
-KS = (0, 1, 2, 3, 4, 8, 9, 64)
+KS = (0, 1, 2, 3, 4, 5, 8, 9, 64)
 
 _cache = {}
 

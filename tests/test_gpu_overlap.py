@@ -1,5 +1,5 @@
 """Box-overlap queries on the GPU (include/shader_ray_overlap.h) against the restatement (tests/overlap_ref.py): every index and
-every count, for the mixed kinds of box of tests/overlap_cases.py, K in {0, 1, 2, 3, 4, 8, 9, 64} with and without counts, on
+every count, for the mixed kinds of box of tests/overlap_cases.py, K in {0, 1, 2, 3, 4, 5, 8, 9, 64} with and without counts, on
 the host and device (torch stream) paths; the tiny trees; the ANY form, box_counts and boxes_touched; surface_voxels; the
 counters; DeviceWorld; after a device refit on the same stream; a count split over launches; and the refusals.  No case is
 skipped or tolerated."""
@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 F = np.float32
 BAD_TREE = -6
-KS = (0, 1, 2, 3, 4, 8, 9, 64)
+KS = (0, 1, 2, 3, 4, 5, 8, 9, 64)
 
 _cache = {}
 

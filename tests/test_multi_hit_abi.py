@@ -112,3 +112,32 @@ def test_argument_errors(pkg):
     assert host(fake, params(64), rays, 0, hits, None) == 0
     assert dev(fake, params(), b, 0, b64, None, None) == 0
     assert cnt(fake, params(), rays, 0, hits, counts, C.byref(tallies)) == 0 and tallies.samples == 0
+
+
+def test_refusal_texts(pkg):
+    """One refusal of each kind leaves in shray_last_error() the text this library has always given for it."""
+    N = pkg._native
+    lib = N.load_multihit()
+    host, cnt = lib.shray_trace_all_hits, lib.shray_trace_all_hits_counters
+    rays, hits, counts = (N.Ray * 2)(), (N.Hit * 16)(), (C.c_int32 * 2)()
+    fake = C.c_void_p(1)   # never read
+
+    def params(max_hits=8, max_leaf_tests=10, struct_size=16):
+        mp = N.MultihitParams()
+        mp.struct_size, mp.max_hits, mp.max_leaf_tests, mp.reserved = struct_size, max_hits, max_leaf_tests, 0
+        return C.byref(mp)
+
+    cases = {
+        "negative ray count -1": lambda: host(fake, params(), rays, -1, hits, counts),
+        "scene or rays is NULL": lambda: host(fake, params(), None, 2, hits, counts),
+        "hits is NULL with max_hits 8": lambda: host(fake, params(), rays, 2, None, counts),
+        "nothing is asked for: max_hits is 0 and counts is NULL": lambda: host(fake, params(0), rays, 2, None, None),
+        "multihit params out of range (max_hits 65 of 0 .. 64, max_leaf_tests 10, reserved 0)":
+            lambda: host(fake, params(65), rays, 2, hits, counts),
+        "shray_multihit_params.struct_size is 12, this library expects 16": lambda: host(fake, params(struct_size=12), rays, 2, hits, counts),
+        "multihit params are NULL": lambda: host(fake, None, rays, 2, hits, counts),
+        "counters is NULL": lambda: cnt(fake, params(), rays, 2, hits, counts, None),
+    }
+    for text, call in cases.items():
+        assert call() == -1, text
+        assert N.load_hip().shray_last_error().decode() == text

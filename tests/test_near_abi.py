@@ -115,3 +115,31 @@ def test_argument_errors(pkg):
     assert host(fake, params(64), pts, 0, out, None) == 0
     assert dev(fake, params(), b, 0, b64, None, None) == 0
     assert cnt(fake, params(), pts, 0, out, counts, C.byref(tallies)) == 0 and tallies.samples == 0
+
+
+def test_refusal_texts(pkg):
+    """One refusal of each kind leaves in shray_last_error() the text this library has always given for it."""
+    N = pkg._native
+    lib = N.load_near()
+    host, cnt = lib.shray_near_triangles, lib.shray_near_triangles_counters
+    pts, out, counts = (N.Point * 2)(), (N.Closest * 16)(), (C.c_int32 * 2)()
+    fake = C.c_void_p(1)   # never read
+
+    def params(max_near=8, struct_size=16):
+        np_ = N.NearParams()
+        np_.struct_size, np_.max_near = struct_size, max_near
+        return C.byref(np_)
+
+    cases = {
+        "negative point count -1": lambda: host(fake, params(), pts, -1, out, counts),
+        "scene or points is NULL": lambda: host(fake, params(), None, 2, out, counts),
+        "out is NULL with max_near 8": lambda: host(fake, params(), pts, 2, None, counts),
+        "nothing is asked for: max_near is 0 and counts is NULL": lambda: host(fake, params(0), pts, 2, None, None),
+        "near params out of range (max_near 65 of 0 .. 64, reserved 0, 0)": lambda: host(fake, params(65), pts, 2, out, counts),
+        "shray_near_params.struct_size is 12, this library expects 16": lambda: host(fake, params(struct_size=12), pts, 2, out, counts),
+        "near params are NULL": lambda: host(fake, None, pts, 2, out, counts),
+        "counters is NULL": lambda: cnt(fake, params(), pts, 2, out, counts, None),
+    }
+    for text, call in cases.items():
+        assert call() == -1, text
+        assert N.load_hip().shray_last_error().decode() == text

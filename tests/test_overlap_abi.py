@@ -114,6 +114,40 @@ def test_argument_errors(pkg):
     assert cnt(fake, params(), boxes, 0, out, counts, C.byref(tallies)) == 0 and tallies.samples == 0
 
 
+def test_refusal_texts(pkg):
+    """One refusal of each kind leaves in shray_last_error() the text this library has always given for it."""
+    N = pkg._native
+    lib = N.load_overlap()
+    host, cnt = lib.shray_overlap_triangles, lib.shray_overlap_triangles_counters
+    buf = np.zeros(1024, np.uint8)
+    base = (buf.ctypes.data + 15) & ~15
+    boxes, out, counts = C.c_void_p(base), C.c_void_p(base + 64), C.c_void_p(base + 640)
+    fake = C.c_void_p(1)   # never read
+
+    def params(k=8, flags=0, struct_size=16):
+        op = N.OverlapParams()
+        op.struct_size, op.max_triangles, op.flags, op.reserved = struct_size, k, flags, 0
+        return C.byref(op)
+
+    cases = {
+        "negative box count -1": lambda: host(fake, params(), boxes, -1, out, counts),
+        "scene or boxes is NULL": lambda: host(fake, params(), None, 2, out, counts),
+        "out is NULL with max_triangles 8": lambda: host(fake, params(), boxes, 2, None, counts),
+        "nothing is asked for: max_triangles is 0 and counts is NULL": lambda: host(fake, params(0), boxes, 2, None, None),
+        "overlap params out of range (max_triangles 65 of 0 .. 64, flags 0x0, reserved 0)": lambda: host(fake, params(65), boxes, 2, out, counts),
+        "shray_overlap_params.struct_size is 12, this library expects 16": lambda: host(fake, params(struct_size=12), boxes, 2, out, counts),
+        "overlap params are NULL": lambda: host(fake, None, boxes, 2, out, counts),
+        # the library's own refusal keeps its place: after the NULL boxes, before the NULL out
+        "SHRAY_OVERLAP_ANY needs max_triangles 0 (it is 8) and counts": lambda: host(fake, params(8, N.OVERLAP_ANY), boxes, 2, None, counts),
+        "the boxes must be 16-byte aligned, the indices and the counts 4-byte aligned":
+            lambda: host(fake, params(), C.c_void_p(base + 4), 2, out, counts),
+        "counters is NULL": lambda: cnt(fake, params(), boxes, 2, out, counts, None),
+    }
+    for text, call in cases.items():
+        assert call() == -1, text
+        assert N.load_hip().shray_last_error().decode() == text
+
+
 def test_a_valid_call_fails_loudly_without_a_gpu(pkg):
     """No CPU fallback: where there is no HIP device a valid query on a real scene is an error with a message, never an answer
     (the scene it needs cannot be created)."""
