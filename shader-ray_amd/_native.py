@@ -23,6 +23,7 @@ INSTANCE_MULTIHIT_LIB = os.path.join(PKG_DIR, "libshray_instance_multihit.so")
 # SHRAY_NEAR_LIB selects an experiment build of the same library (profiles/near_bench.py --ab); unset in normal use
 NEAR_LIB = os.environ.get("SHRAY_NEAR_LIB") or os.path.join(PKG_DIR, "libshray_near.so")
 OVERLAP_LIB = os.path.join(PKG_DIR, "libshray_overlap.so")
+INTERSECT_LIB = os.path.join(PKG_DIR, "libshray_intersect.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
 HIP_LIB = os.environ.get("SHRAY_HIP_LIB") or os.path.join(PKG_DIR, "libshray_hip.so")
 
@@ -431,6 +432,34 @@ OVERLAP_SYMBOLS = [
                                                    C.POINTER(Counters)]),
 ]
 
+# include/shader_ray_intersect.h ---------------------------------------------------------------------------
+INTERSECT_MAX = 64
+INTERSECT_ANY = 1
+INTERSECT_SKIP_SHARED = 2
+
+
+class Triangle(C.Structure):
+    """shray_triangle: three corners with a pad after each (48 bytes)."""
+    _fields_ = [("a", C.c_float * 3), ("pad0", C.c_float), ("b", C.c_float * 3), ("pad1", C.c_float), ("c", C.c_float * 3),
+                ("pad2", C.c_float)]
+
+
+class IntersectParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_triangles", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
+INTERSECT_SYMBOLS = [
+    ("shray_intersect_params_init", None, [C.POINTER(IntersectParams)]),
+    ("shray_intersect_triangles_device", C.c_int, [C.c_void_p, C.POINTER(IntersectParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]),
+    ("shray_intersect_triangles", C.c_int, [C.c_void_p, C.POINTER(IntersectParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("shray_intersect_triangles_counters", C.c_int, [C.c_void_p, C.POINTER(IntersectParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                     C.POINTER(Counters)]),
+    ("shray_intersect_self_device", C.c_int, [C.c_void_p, C.POINTER(IntersectParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    ("shray_intersect_self", C.c_int, [C.c_void_p, C.POINTER(IntersectParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+]
+
 # include/shader_ray_instance_multihit.h -------------------------------------------------------------------
 INSTANCE_MULTIHIT_SYMBOLS = [
     ("shray_trace_instances_all_hits_device", C.c_int, [C.c_void_p, C.POINTER(MultihitParams), C.c_void_p, C.c_int64, C.c_void_p,
@@ -542,6 +571,11 @@ def load_near():
 def load_overlap():
     """Loads the box-overlap query library (libshray_overlap.so)."""
     return _load_client(OVERLAP_LIB, OVERLAP_SYMBOLS)
+
+
+def load_intersect():
+    """Loads the triangle-intersection query library (libshray_intersect.so)."""
+    return _load_client(INTERSECT_LIB, INTERSECT_SYMBOLS)
 
 
 def load_instance_multihit():

@@ -436,6 +436,119 @@ class Scene:
         host boxes, a tensor for GPU boxes."""
         return self.triangles_in_boxes(boxes, max_triangles=0, counts=True, any_only=True)[1] != 0
 
+    def intersecting_triangles(self, triangles, max_triangles: int = 8, counts: bool = True, counters: bool = False, any_only: bool = False,
+                               skip_shared: bool = False):
+        """Triangle-intersection queries (include/shader_ray_intersect.h): per query triangle the number of scene triangles
+        it intersects and the `max_triangles` smallest of their indices in ascending order, the other slots SHRAY_HIT_MISS
+        (-1).  `triangles`: a TRIANGLE_DTYPE array or [n, 3, 3] / [n, 9] (a, b, c) / [n, 12] (the shray_triangle layout)
+        float32 takes the blocking host path (shray_intersect_triangles) and returns (indices: int32 [n, max_triangles],
+        counts: int32 [n]); a float32 [n, 9] / [n, 12] GPU tensor on the scene's device takes the device path
+        (shray_intersect_triangles_device) on the current torch stream and returns tensors of the same shapes.  counts=False
+        returns None for the counts; max_triangles = 0 returns None for the indices.  any_only=True (with max_triangles = 0)
+        sets SHRAY_INTERSECT_ANY: the count is 1 or 0 and the walk stops at the first member.  skip_shared=True sets
+        SHRAY_INTERSECT_SKIP_SHARED: a scene triangle with a corner equal to one of the query's is not a member.
+        counters=True (host triangles only) also returns the walk's counters (shray_intersect_triangles_counters)."""
+        lib = N.load_intersect()
+        return _first_k(self._handle, (lib.shray_intersect_triangles_device, lib.shray_intersect_triangles,
+                                       lib.shray_intersect_triangles_counters),
+                        intersect_params(max_triangles, any_only, skip_shared), max_triangles, "max_triangles", triangles, "triangles",
+                        self._device_triangles, _host_triangles, np.int32, (), False, counts, counters)
+
+    def _device_triangles(self, triangles):
+        """a float32 [n, 9] / [n, 12] GPU tensor on the scene's device as a contiguous [n, 12] shray_triangle tensor"""
+        import torch
+        if triangles.device.index != self.device_index():
+            raise ValueError(f"triangles are on {triangles.device}, the scene on cuda:{self.device_index()}")
+        if triangles.dtype != torch.float32 or triangles.dim() != 2 or triangles.shape[1] not in (9, 12):
+            raise ValueError("a GPU triangle tensor must be float32 [n, 9] (a, b, c) or [n, 12] (the shray_triangle layout)")
+        if triangles.shape[1] == 12:
+            return triangles.contiguous()
+        tr = torch.zeros((len(triangles), 12), dtype=torch.float32, device=triangles.device)
+        for corner in range(3):
+            tr[:, 4 * corner:4 * corner + 3] = triangles[:, 3 * corner:3 * corner + 3]
+        return tr
+
+    def intersecting_triangles_into(self, triangles_ptr: int, count: int, out_ptr: int, counts_ptr: int = 0, max_triangles: int = 8,
+                                    any_only: bool = False, skip_shared: bool = False, stream_ptr: int = 0):
+        """Asynchronous triangle-intersection queries on device memory of the scene's device
+        (shray_intersect_triangles_device): `count` shray_triangle records at `triangles_ptr` -> count * max_triangles int32
+        indices at `out_ptr` (0 iff max_triangles is 0) and, unless `counts_ptr` is 0, `count` int32 counts there, on a HIP
+        stream (`stream_ptr`)."""
+        op = intersect_params(max_triangles, any_only, skip_shared)
+        N.check(N.load_intersect().shray_intersect_triangles_device(self._handle, C.byref(op), C.c_void_p(triangles_ptr), count,
+                                                                    C.c_void_p(out_ptr or None), C.c_void_p(counts_ptr or None),
+                                                                    C.c_void_p(stream_ptr)))
+
+    def intersection_counts(self, triangles, skip_shared: bool = False):
+        """How many scene triangles each query triangle intersects (intersecting_triangles with max_triangles = 0): int32 [n],
+        numpy for host triangles, a tensor for GPU triangles."""
+        return self.intersecting_triangles(triangles, max_triangles=0, counts=True, skip_shared=skip_shared)[1]
+
+    def triangles_intersected(self, triangles, skip_shared: bool = False):
+        """Whether each query triangle intersects any scene triangle (SHRAY_INTERSECT_ANY: the walk stops at the first one):
+        bool [n], numpy for host triangles, a tensor for GPU triangles."""
+        return self.intersecting_triangles(triangles, max_triangles=0, counts=True, any_only=True, skip_shared=skip_shared)[1] != 0
+
+    def triangle_count(self) -> int:
+        """The number of triangles of the scene."""
+        corners = C.c_int32()
+        N.check(N.load_refit().shray_scene_geometry_counts(self._handle, C.byref(corners), None))
+        return corners.value // 3
+
+    def self_intersections(self, max_triangles: int = 8, counts: bool = True, any_only: bool = False, skip_shared: bool = True,
+                           first: int = 0, count: int | None = None, device: bool = False):
+        """The scene's own triangles [first, first + count) as the queries (shray_intersect_self; count=None: up to the last
+        one), read from the scene's positions as they are when the query runs.  Returns (indices: int32 [count, max_triangles],
+        counts: int32 [count]) as numpy arrays from the blocking form, or with device=True as tensors on the scene's device
+        enqueued on the current torch stream (shray_intersect_self_device).  skip_shared defaults to True here: without it
+        every triangle finds itself and its neighbours.  max_triangles = 0 returns None for the indices, counts=False None
+        for the counts; any_only as for intersecting_triangles."""
+        if max_triangles == 0 and not counts:
+            raise ValueError("nothing is asked for: max_triangles is 0 and counts is False")
+        triangles = self.triangle_count()
+        if count is None:
+            count = max(triangles - first, 0)
+        op = intersect_params(max_triangles, any_only, skip_shared)
+        lib = N.load_intersect()
+        rows = count if first >= 0 and 0 <= count <= triangles - first else 0   # (the library refuses any other range)
+        if device:
+            import torch
+            where = torch.device("cuda", self.device_index())
+            out = torch.empty((rows, max_triangles), dtype=torch.int32, device=where) if max_triangles > 0 else None
+            n = torch.empty((rows,), dtype=torch.int32, device=where) if counts else None
+            N.check(lib.shray_intersect_self_device(self._handle, C.byref(op), first, count,
+                                                    C.c_void_p(out.data_ptr() if out is not None else None),
+                                                    C.c_void_p(n.data_ptr() if n is not None else None),
+                                                    C.c_void_p(torch.cuda.current_stream(where).cuda_stream)))
+            return out, n
+        out = np.empty((rows, max_triangles), np.int32) if max_triangles > 0 else None
+        n = np.empty((rows,), np.int32) if counts else None
+        N.check(lib.shray_intersect_self(self._handle, C.byref(op), first, count,
+                                         out.ctypes.data_as(C.c_void_p) if out is not None else None,
+                                         n.ctypes.data_as(C.c_void_p) if n is not None else None))
+        return out, n
+
+    def self_intersections_into(self, first: int, count: int, out_ptr: int, counts_ptr: int = 0, max_triangles: int = 8,
+                                any_only: bool = False, skip_shared: bool = True, stream_ptr: int = 0):
+        """Asynchronous self-intersection queries (shray_intersect_self_device): the scene's triangles [first, first + count)
+        -> count * max_triangles int32 indices at `out_ptr` (0 iff max_triangles is 0) and, unless `counts_ptr` is 0, `count`
+        int32 counts there, device memory of the scene's device, on a HIP stream (`stream_ptr`)."""
+        op = intersect_params(max_triangles, any_only, skip_shared)
+        N.check(N.load_intersect().shray_intersect_self_device(self._handle, C.byref(op), first, count, C.c_void_p(out_ptr or None),
+                                                               C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+
+    def is_self_intersecting(self) -> bool:
+        """Whether any triangle of the scene intersects one it shares no corner with (SHRAY_INTERSECT_ANY |
+        SHRAY_INTERSECT_SKIP_SHARED over every triangle)."""
+        return bool(self.self_intersections(max_triangles=0, counts=True, any_only=True, skip_shared=True)[1].any())
+
+    def intersections_with(self, other: "Scene", max_triangles: int = 8, counts: bool = True, any_only: bool = False,
+                           skip_shared: bool = False):
+        """Mesh against mesh: the queries are the other scene's current triangles (other.geometry(), so after its refits), in
+        its triangle order; the blocking host path of intersecting_triangles on this scene."""
+        theirs = np.asarray(other.geometry()["vertex_positions"], np.float32).reshape(-1, 9)
+        return self.intersecting_triangles(theirs, max_triangles=max_triangles, counts=counts, any_only=any_only, skip_shared=skip_shared)
+
     def surface_voxels(self, origin, cell, dims, device=None):
         """The occupancy grid of the surface: bool [nx, ny, nz], voxel (i, j, k) set iff a triangle touches the box
         lo = origin + (i, j, k) * cell, hi = origin + (i + 1, j + 1, k + 1) * cell.  Each bound is one fp32 multiply and one
@@ -560,8 +673,8 @@ def _device_rays(rays, device_index: int, owner: str):
 
 def _first_k(handle, functions, params, k: int, k_name: str, items, kind: str, on_device, on_host, record_dtype, trailing, second: bool,
              counts: bool, counters: bool):
-    """The counted first-K queries (all-hits rays, their instanced form, within-radius, box-overlap): per item a count and
-    its first `k` records.  `functions`: the library's device form, blocking form and blocking form with counters, called with
+    """The counted first-K queries (all-hits rays, their instanced form, within-radius, box-overlap, triangle-intersection): per item a
+    count and its first `k` records.  `functions`: the library's device form, blocking form and blocking form with counters, called with
     (`handle`, `params`, items, n, records[, second], counts, ...).  `items` (`kind`: "rays", "points", "boxes"): a GPU tensor
     takes the device path on the current torch stream, through `on_device` (which refuses another device or layout), anything
     else the blocking path, through `on_host`.  The records are an int32 [n, k, *trailing] tensor or a `record_dtype` [n, k]
@@ -681,6 +794,41 @@ def overlap_params(max_triangles: int = 8, any_only: bool = False) -> N.OverlapP
     op.max_triangles = max_triangles
     op.flags = N.OVERLAP_ANY if any_only else 0
     return op
+
+
+def intersect_params(max_triangles: int = 8, any_only: bool = False, skip_shared: bool = False) -> N.IntersectParams:
+    op = N.IntersectParams()
+    N.load_intersect().shray_intersect_params_init(C.byref(op))
+    op.max_triangles = max_triangles
+    op.flags = (N.INTERSECT_ANY if any_only else 0) | (N.INTERSECT_SKIP_SHARED if skip_shared else 0)
+    return op
+
+
+# a triangle buffer of the triangle-intersection query (include/shader_ray_intersect.h): 48 bytes per element
+TRIANGLE_DTYPE = np.dtype([("a", np.float32, 3), ("pad0", np.float32), ("b", np.float32, 3), ("pad1", np.float32), ("c", np.float32, 3),
+                           ("pad2", np.float32)])
+
+
+def make_triangles(a, b=None, c=None) -> np.ndarray:
+    """A TRIANGLE_DTYPE array from [n, 3, 3] or [n, 9] corners, or from three [n, 3] arrays a, b, c."""
+    if b is None:
+        corners = np.asarray(a, np.float32).reshape(-1, 3, 3)
+        a, b, c = corners[:, 0], corners[:, 1], corners[:, 2]
+    a = np.asarray(a, np.float32).reshape(-1, 3)
+    out = np.zeros(len(a), TRIANGLE_DTYPE)
+    out["a"] = a
+    out["b"] = np.asarray(b, np.float32).reshape(-1, 3)
+    out["c"] = np.asarray(c, np.float32).reshape(-1, 3)
+    return out
+
+
+def _host_triangles(triangles) -> np.ndarray:
+    """Scene.intersecting_triangles's host triangle forms as one contiguous TRIANGLE_DTYPE array."""
+    triangles = np.asarray(triangles)
+    if triangles.dtype != TRIANGLE_DTYPE and triangles.ndim == 3 and triangles.shape[1:] == (3, 3):
+        triangles = triangles.reshape(-1, 9)
+    return _host_records(triangles, TRIANGLE_DTYPE, 9, 12, make_triangles, None, None,
+                         "triangles must be a TRIANGLE_DTYPE array or [n, 3, 3] / [n, 9] (a, b, c) / [n, 12] (shray_triangle) float32")
 
 
 # a box buffer of the box-overlap query (include/shader_ray_overlap.h): 32 bytes per element
