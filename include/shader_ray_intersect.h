@@ -72,7 +72,8 @@
  * narrower than the box-overlap query's -27 .. 44 at the top.  Projections on nq cross f and nt cross e are fourth powers of a
  * coordinate difference: above the range they overflow (and an infinite or NaN projection stops separating), below it they
  * lose bits to underflow.  Outside the range the contract above still holds bit for bit: the set is what the arithmetic above
- * gives, and it always stays within stage 0's.
+ * gives, and it always stays within stage 0's (tests/test_intersect_scale_reference.py and tests/test_gpu_intersect_scale.py:
+ * 2^-80 to 2^64, on the scenes as loaded the sets are kept for -33 <= k <= 29 as well).
  *
  * Errors: count == 0 is a no-op.  A wrong struct_size, K outside [0, SHRAY_INTERSECT_MAX], unknown flag bits, a nonzero
  * reserved field, SHRAY_INTERSECT_ANY with K != 0 or without counts, K == 0 together with no counts (nothing is asked for;
