@@ -20,6 +20,7 @@ SDF_LIB = os.path.join(PKG_DIR, "libshray_sdf.so")
 WINDING_LIB = os.path.join(PKG_DIR, "libshray_winding.so")
 MULTIHIT_LIB = os.path.join(PKG_DIR, "libshray_multihit.so")
 INSTANCE_MULTIHIT_LIB = os.path.join(PKG_DIR, "libshray_instance_multihit.so")
+INSTANCE_POINT_LIB = os.path.join(PKG_DIR, "libshray_instance_point.so")
 # SHRAY_NEAR_LIB selects an experiment build of the same library (profiles/near_bench.py --ab); unset in normal use
 NEAR_LIB = os.environ.get("SHRAY_NEAR_LIB") or os.path.join(PKG_DIR, "libshray_near.so")
 OVERLAP_LIB = os.path.join(PKG_DIR, "libshray_overlap.so")
@@ -470,6 +471,14 @@ INSTANCE_MULTIHIT_SYMBOLS = [
                                                           C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
 ]
 
+# include/shader_ray_instance_point.h ----------------------------------------------------------------------
+INSTANCE_POINT_SYMBOLS = [
+    ("shray_closest_points_instances_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("shray_closest_points_instances", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("shray_closest_points_instances_counters", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                          C.POINTER(Counters)]),
+]
+
 _host = None
 _hip = None
 _clients = {}   # path -> the loaded client library of libshray_hip.so
@@ -581,6 +590,11 @@ def load_intersect():
 def load_instance_multihit():
     """Loads the instanced all-hits library (libshray_instance_multihit.so: depends on libshray_instance.so too)."""
     return _load_client(INSTANCE_MULTIHIT_LIB, INSTANCE_MULTIHIT_SYMBOLS)
+
+
+def load_instance_point():
+    """Loads the instanced closest-point library (libshray_instance_point.so: depends on libshray_instance.so too)."""
+    return _load_client(INSTANCE_POINT_LIB, INSTANCE_POINT_SYMBOLS)
 
 
 def check_dist(code: int):

@@ -583,17 +583,47 @@ struct Staging {
     hipEvent_t copied = nullptr;
 };
 
-// What the device update keeps per set: its scratch (sized by the set's count, allocated by the first device update), the
-// device copy of the current transforms, and what it last uploaded.
+// waits for every copy of `staging` and frees its pinned memory
+void release(std::vector<Staging> &staging)
+{
+    for (Staging &s : staging) {
+        if (s.copied)
+            (void)hipEventSynchronize(s.copied);
+        if (s.host)
+            (void)hipHostFree(s.host);
+        if (s.copied)
+            (void)hipEventDestroy(s.copied);
+    }
+    staging.clear();
+}
+
+// The device copy of the set's current object-to-world maps, float [12 n]: what the device update keeps between its calls and
+// what a query that needs the forward maps reads (shrayi_instance_set_forward_maps).  Allocated by whichever comes first; a
+// host update leaves it behind the host copy (`stale`), and the next reader stages the upload on its own stream.  `uploaded`
+// is recorded after that copy, so that a reader on another stream can wait for it without the host.
+struct ForwardMaps {
+    DeviceBuffer transforms;
+    bool stale = true;                        // behind the host copy: before the first use, and after a host update
+    std::vector<Staging> staging;
+    hipEvent_t uploaded = nullptr;
+    bool recorded = false;
+    ~ForwardMaps()
+    {
+        release(staging);
+        if (uploaded)
+            (void)hipEventDestroy(uploaded);
+    }
+};
+
+// What the device update keeps per set: its scratch (sized by the set's count, allocated by the first device update) and what
+// it last uploaded.
 struct DeviceUpdate {
     uint32_t n = 0;
     int depth = 0;                            // levels of splits: ceil(log2 n)
     std::vector<shray_scene *> distinct;      // the member scenes in scene-slot order (the host's: first appearance)
     std::vector<SceneView> staged;            // what `views` holds, once views_staged
     bool views_staged = false;
-    bool transforms_stale = true;             // `transforms` is behind the host copy: the first call, and after a host update
     DeviceBuffer words;                       // int32 [0]: the refusal word, [1]: the status of the last update
-    DeviceBuffer transforms;                  // float [12 n]: the set's current object-to-world maps
     DeviceBuffer records, leaves, nodes, centres, keys, sorted_keys, ids, lists[2], left_of, flags, offsets, views, temp;
     size_t temp_bytes = 0;
     std::vector<Staging> staging;
@@ -601,14 +631,7 @@ struct DeviceUpdate {
     bool enqueued = false;
     ~DeviceUpdate()
     {
-        for (Staging &s : staging) {
-            if (s.copied)
-                (void)hipEventSynchronize(s.copied);
-            if (s.host)
-                (void)hipHostFree(s.host);
-            if (s.copied)
-                (void)hipEventDestroy(s.copied);
-        }
+        release(staging);
         if (finished)
             (void)hipEventDestroy(finished);
     }
@@ -622,6 +645,7 @@ struct shray_instance_set {
     Prepared host;
     SetDevice dev;
     std::unique_ptr<DeviceUpdate> update;   // the device update's state, once one was made
+    std::unique_ptr<ForwardMaps> maps;      // the device copy of object_to_world, once something asked for it
     bool host_stale = false;                // host.object_to_world / world_to_object may be behind a device update
 };
 
@@ -652,7 +676,6 @@ int make_update(shray_instance_set *set, hipStream_t stream, std::unique_ptr<Dev
             u->distinct.push_back(s);
     const size_t m = 3 * (size_t)n;
     HIP_TRY(u->words.alloc(2 * sizeof(int32_t)));
-    HIP_TRY(u->transforms.alloc(12 * (size_t)n * sizeof(float)));
     HIP_TRY(u->records.alloc(4 * (size_t)n * sizeof(float4)));
     HIP_TRY(u->leaves.alloc((size_t)n * sizeof(TopNode)));
     HIP_TRY(u->nodes.alloc((2 * (size_t)n - 1) * sizeof(TopNode)));
@@ -684,10 +707,10 @@ int make_update(shray_instance_set *set, hipStream_t stream, std::unique_ptr<Dev
 
 // `bytes` of host memory to device memory at `dst` on `stream`, through pinned memory that is reused once its copy is done
 // (no host wait)
-int stage(DeviceUpdate &u, hipStream_t stream, void *dst, const void *src, size_t bytes)
+int stage(std::vector<Staging> &staging, hipStream_t stream, void *dst, const void *src, size_t bytes)
 {
     Staging *s = nullptr;
-    for (Staging &c : u.staging) {
+    for (Staging &c : staging) {
         const hipError_t q = hipEventQuery(c.copied);
         if (q == hipSuccess && c.bytes >= bytes) {
             s = &c;
@@ -705,12 +728,37 @@ int stage(DeviceUpdate &u, hipStream_t stream, void *dst, const void *src, size_
             (void)hipHostFree(c.host);
             return fail(SHRAY_ERR_DEVICE, "hipEventCreateWithFlags failed: %s", hipGetErrorString(e));
         }
-        u.staging.push_back(c);
-        s = &u.staging.back();
+        staging.push_back(c);
+        s = &staging.back();
     }
     memcpy(s->host, src, bytes);
     HIP_TRY(hipMemcpyAsync(dst, s->host, bytes, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipEventRecord(s->copied, stream));
+    return SHRAY_OK;
+}
+
+// The device copy of the set's object-to-world maps, current for work enqueued on `stream` after this call: made on first
+// use (12 n floats, nothing else), uploaded from the host copy on `stream` when it is behind it, else `stream` waits for the
+// last upload, which may have run on another stream.  No host wait.  (The set's device is current.)
+int current_maps(shray_instance_set *set, hipStream_t stream)
+{
+    if (!set->maps) {
+        auto m = std::make_unique<ForwardMaps>();
+        HIP_TRY(m->transforms.alloc(12 * set->scenes.size() * sizeof(float)));
+        HIP_TRY(hipEventCreateWithFlags(&m->uploaded, hipEventDisableTiming));
+        set->maps = std::move(m);
+    }
+    ForwardMaps &m = *set->maps;
+    if (m.stale) {
+        const int rc = stage(m.staging, stream, m.transforms.p, set->host.object_to_world.data(), 12 * set->scenes.size() * sizeof(float));
+        if (rc)
+            return rc;
+        HIP_TRY(hipEventRecord(m.uploaded, stream));
+        m.recorded = true;
+        m.stale = false;
+    } else if (m.recorded) {
+        HIP_TRY(hipStreamWaitEvent(stream, m.uploaded, 0));
+    }
     return SHRAY_OK;
 }
 
@@ -727,7 +775,7 @@ int refresh_host(shray_instance_set *set)
     std::vector<float> transforms(12 * n);
     HIP_TRY(hipEventSynchronize(set->update->finished));
     HIP_TRY(hipMemcpy(records.data(), set->dev.records, records.size() * sizeof(float4), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(transforms.data(), set->update->transforms.p, transforms.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(transforms.data(), set->maps->transforms.p, transforms.size() * sizeof(float), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i)
         for (int r = 0; r < 3; ++r) {
             const float4 &w = records[4 * i + r];
@@ -775,24 +823,21 @@ int update_device(shray_instance_set *set, const float *d_object_to_world, hipSt
     }
     const size_t view_bytes = views.size() * sizeof(SceneView);
     if (!u.views_staged || memcmp(views.data(), u.staged.data(), view_bytes) != 0) {
-        rc = stage(u, stream, u.views.p, views.data(), view_bytes);
+        rc = stage(u.staging, stream, u.views.p, views.data(), view_bytes);
         if (rc)
             return rc;
         u.staged = views;
         u.views_staged = true;
     }
-    if (u.transforms_stale) {
-        rc = stage(u, stream, u.transforms.p, set->host.object_to_world.data(), 12 * (size_t)n * sizeof(float));
-        if (rc)
-            return rc;
-        u.transforms_stale = false;
-    }
+    if ((rc = current_maps(set, stream)))
+        return rc;
+    const DeviceBuffer &transforms = set->maps->transforms;
     int32_t *refused = u.words.as<int32_t>();
     const size_t m = 3 * (size_t)n;
     const dim3 grid(blocks_of(n)), block(kUpdateBlock);
     HIP_TRY(hipMemsetAsync(refused, 0x7f, sizeof(int32_t), stream));   // kNoRefusal
     // 1. one pass per instance
-    hipLaunchKernelGGL(iu_instances, grid, block, 0, stream, n, d_object_to_world ? d_object_to_world : u.transforms.as<const float>(),
+    hipLaunchKernelGGL(iu_instances, grid, block, 0, stream, n, d_object_to_world ? d_object_to_world : transforms.as<const float>(),
                        (const float4 *)set->dev.records, u.views.as<const SceneView>(), u.records.as<float4>(), u.leaves.as<TopNode>(),
                        u.centres.as<double>(), u.keys.as<uint64_t>(), refused);
     if ((rc = launched("instance update")))
@@ -826,7 +871,7 @@ int update_device(shray_instance_set *set, const float *d_object_to_world, hipSt
     const uint32_t view_words = (uint32_t)(view_bytes / sizeof(uint32_t));
     hipLaunchKernelGGL(iu_commit, dim3(std::min(blocks_of(12 * (size_t)n), 1024u)), block, 0, stream, n, u.nodes.as<const TopNode>(),
                        u.records.as<const float4>(), d_object_to_world, u.views.as<const uint32_t>(), view_words, set->dev.nodes,
-                       set->dev.records, d_object_to_world ? u.transforms.as<float>() : nullptr, (uint32_t *)set->dev.views,
+                       set->dev.records, d_object_to_world ? transforms.as<float>() : nullptr, (uint32_t *)set->dev.views,
                        (const int32_t *)refused, refused + 1);
     if ((rc = launched("instance update")))
         return rc;
@@ -959,8 +1004,8 @@ int shray_instance_set_update(shray_instance_set *set, const float *object_to_wo
     set->host = std::move(p);
     set->dev = d;
     set->host_stale = false;
-    if (set->update)
-        set->update->transforms_stale = true;
+    if (set->maps)
+        set->maps->stale = true;
     return SHRAY_OK;
 }
 
@@ -1049,6 +1094,24 @@ int shrayi_instance_set_device_arrays(const shray_instance_set *set, ShrayInstan
     out->count = (int32_t)set->scenes.size();
     out->scene_count = (int32_t)set->distinct.size();
     out->device = set->host.device;
+    return SHRAY_OK;
+}
+
+// For libshray_instance_point.so, not in the header (top_level.h): the set's current object_to_world floats on its device,
+// float [count][12], the very floats it was created or last updated with, for a launch enqueued on `hip_stream` after this
+// call.  After a host update (and on first use) the upload is staged on that stream; after a device update the copy is the
+// one that update's commit wrote, in stream order.  Host-only; makes the set's device current and waits for nothing.
+int shrayi_instance_set_forward_maps(shray_instance_set *set, void *hip_stream, const float **d_maps)
+{
+    if (!set || !d_maps)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "set or d_maps is NULL");
+    *d_maps = nullptr;
+    int rc = use_device(set->host.device);
+    if (rc)
+        return rc;
+    if ((rc = current_maps(set, (hipStream_t)hip_stream)))
+        return rc;
+    *d_maps = set->maps->transforms.as<const float>();
     return SHRAY_OK;
 }
 

@@ -1,7 +1,8 @@
 // top_level.h -- what the kernels that walk an instance set's top level share (instance.hip: closest and any hit;
 // instance_multihit/instance_multihit.hip: all hits): the node and record layout, a lane's widened slab test of a top-level
-// box, the object ray (include/shader_ray_instance.h), and the accessor through which another library reads a set's device
-// arrays.  Internal to the libraries; no kernel is defined here.
+// box, the object ray (include/shader_ray_instance.h), and the accessors through which another library reads a set's device
+// arrays and its forward maps (instance_point/instance_point.hip: closest points).  Internal to the libraries; no kernel is
+// defined here.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -77,3 +78,8 @@ struct ShrayInstanceSetDevice {
 
 // Not in the header: for libshray_instance_multihit.so.  Host-only; waits for nothing and touches no device.
 extern "C" int shrayi_instance_set_device_arrays(const shray_instance_set *set, ShrayInstanceSetDevice *out);
+
+// Not in the header: for libshray_instance_point.so.  The set's current object_to_world floats on its device, float
+// [count][12], for a launch enqueued on `hip_stream` after this call (an upload that is due is staged on that stream).
+// Host-only; makes the set's device current and waits for nothing.
+extern "C" int shrayi_instance_set_forward_maps(shray_instance_set *set, void *hip_stream, const float **d_maps);

@@ -1205,6 +1205,46 @@ class InstanceSet:
         int32 [n], numpy for host rays, a tensor for GPU rays."""
         return self.trace_all_hits(rays, max_hits=0, counts=True, max_leaf_tests=max_leaf_tests)[2]
 
+    def closest_points(self, points, max_dist2=None, counters: bool = False):
+        """Instanced closest-point queries (include/shader_ray_instance_point.h): the nearest point of any instance's surface to
+        each world-space point, measured on the instances' triangles mapped to the world by the set's object-to-world floats.
+        `points` and `max_dist2` as for Scene.closest_points.  Host points take the blocking path and return (records:
+        CLOSEST_DTYPE [n], instances: int32 [n]); a float32 [n, 3] / [n, 4] GPU tensor on the set's device takes the device
+        path on the current torch stream and returns (int32 [n, 8] tensor of shray_closest records, int32 [n] tensor).  A miss
+        has instance -1.  counters=True (host points only) also returns the walks' counters."""
+        lib = N.load_instance_point()
+        points = _host_if_cpu(points)
+        if _is_torch(points):
+            import torch
+            if counters:
+                raise ValueError("counters are counted on the host path: pass host points")
+            if points.device.index != self.device:
+                raise ValueError(f"points are on {points.device}, the set on cuda:{self.device}")
+            pts = self._scenes[0]._device_points(points, max_dist2)
+            out = torch.empty((len(pts), 8), dtype=torch.int32, device=pts.device)
+            inst = torch.empty(len(pts), dtype=torch.int32, device=pts.device)
+            stream = torch.cuda.current_stream(pts.device)
+            N.check(lib.shray_closest_points_instances_device(self._handle, C.c_void_p(pts.data_ptr()), len(pts), C.c_void_p(out.data_ptr()),
+                                                              C.c_void_p(inst.data_ptr()), C.c_void_p(stream.cuda_stream)))
+            return out, inst
+        pts = _host_points(points, max_dist2)
+        out = np.empty(len(pts), CLOSEST_DTYPE)
+        inst = np.empty(len(pts), np.int32)
+        args = (self._handle, pts.ctypes.data_as(C.c_void_p), len(pts), out.ctypes.data_as(C.c_void_p), inst.ctypes.data_as(C.c_void_p))
+        if counters:
+            c = N.Counters()
+            N.check(lib.shray_closest_points_instances_counters(*args, C.byref(c)))
+            return out, inst, c.as_dict()
+        N.check(lib.shray_closest_points_instances(*args))
+        return out, inst
+
+    def closest_points_into(self, points_ptr: int, count: int, out_ptr: int, instances_ptr: int = 0, stream_ptr: int = 0):
+        """Asynchronous instanced closest-point queries on device memory of the set's device
+        (shray_closest_points_instances_device): `count` shray_point records at `points_ptr` -> `count` shray_closest records at
+        `out_ptr` and, unless `instances_ptr` is 0, int32 instance indices there, on a HIP stream (`stream_ptr`)."""
+        N.check(N.load_instance_point().shray_closest_points_instances_device(
+            self._handle, C.c_void_p(points_ptr), count, C.c_void_p(out_ptr), C.c_void_p(instances_ptr or None), C.c_void_p(stream_ptr)))
+
     def close(self):
         if getattr(self, "_handle", None):
             self._lib.shray_instance_set_destroy(self._handle)
