@@ -14,7 +14,6 @@ import point_query_ref as R
 F = np.float32
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 EYE = np.eye(3, 4, dtype=F)
-O = R.NumpyOps
 
 
 def rotation(rng):
@@ -53,21 +52,7 @@ def random_map(rng, kind, scale=1.0):
     return (np.concatenate([A, b[:, None]], axis=1) * scale).astype(F)
 
 
-def columns(a):
-    return tuple(a[..., k] for k in range(3))
-
-
-def bound(p, lo, hi):
-    """box_bound for points p [n, 3] against one box: float32 [n]"""
-    with np.errstate(all="ignore"):
-        return R.box_bound(O, columns(p), columns(lo), columns(hi))
-
-
-def pair_dist2(p, corners):
-    """dist2 [n points, t triangles] of the header's per-triangle formula on world corners [t, 3, 3]"""
-    with np.errstate(all="ignore"):
-        tri = lambda k: tuple(corners[None, :, k, c] for c in range(3))
-        return R.closest_on_triangles(O, tuple(p[:, c:c + 1] for c in range(3)), tri(0), tri(1), tri(2))
+bound, pair_dist2, median_tree, restated_walk = IP.bound, IP.pair_dist2, IP.median_tree, IP.restated_walk      # (they live there)
 
 
 # 1 ---------------------------------------------------------------------------------------------------------------------------
@@ -106,78 +91,6 @@ def lobed_positions(pkg):
         return np.asarray(world.arrays()["vertex_positions"], F).copy()
     finally:
         world.close()
-
-
-def median_tree(corners, leaf=6):
-    """A median-split tree over triangles [t, 3, 3] with the exact minima and maxima of the vertices below every node: a list
-    of (lo, hi, left, right, triangle ids or None), the root first."""
-    nodes = []
-
-    def build(ids):
-        at = len(nodes)
-        v = corners[ids].reshape(-1, 3)
-        nodes.append(None)
-        if len(ids) <= leaf:
-            nodes[at] = (v.min(0), v.max(0), -1, -1, ids)
-            return at
-        c = corners[ids].mean(1)
-        axis = int(np.argmax(c.max(0) - c.min(0)))
-        order = ids[np.argsort(c[:, axis], kind="stable")]
-        left, right = build(order[:len(order) // 2]), build(order[len(order) // 2:])
-        nodes[at] = (v.min(0), v.max(0), left, right, None)
-        return at
-
-    build(np.arange(len(corners)))
-    return nodes
-
-
-def restated_walk(corners, maps, points, order):
-    """The kernel's walk in numpy, all points at once: per instance (in `order`) the tree of the object corners, a node skipped
-    for a point only when the bound of its IMAGE box is above the point's best dist2, a leaf's triangles mapped and tested in
-    turn with the header's "better" rule on (dist2, instance, triangle).  Returns (records, instances, triangle tests)."""
-    tree = median_tree(corners)
-    n = len(points)
-    p = np.ascontiguousarray(points["p"])
-    md = points["max_dist2"]
-    walk = np.isfinite(p).all(1) & (md >= 0)
-    best = md.copy()
-    tri, inst = np.full(n, -1, np.int64), np.full(n, -1, np.int64)
-    q, u, v, region = p.copy(), np.zeros(n, F), np.zeros(n, F), np.full(n, -1, np.int64)
-    tests = 0
-
-    def visit(M, i, at, ids):
-        nonlocal tests
-        lo, hi, left, right, members = tree[at]
-        ilo, ihi = IP.image_box(M, lo, hi)
-        ids = ids[~(bound(p[ids], ilo, ihi) > best[ids])]
-        if not len(ids):
-            return
-        if members is None:
-            l_lo, l_hi = IP.image_box(M, *tree[left][:2])
-            r_lo, r_hi = IP.image_box(M, *tree[right][:2])
-            first = p[ids[:1]]
-            near, far = (right, left) if bound(first, r_lo, r_hi)[0] < bound(first, l_lo, l_hi)[0] else (left, right)
-            visit(M, i, near, ids)
-            visit(M, i, far, ids)
-            return
-        world = IP.map_corners(M, corners[members]).reshape(-1, 3, 3)
-        cq, d2, cu, cv, cr = pair_dist2(p[ids], world)
-        tests += d2.size
-        for k, t in enumerate(members):
-            d = d2[:, k]
-            b, bt, bi = best[ids], tri[ids], inst[ids]
-            better = np.where(bt < 0, d <= b, (d < b) | ((d == b) & ((i < bi) | ((i == bi) & (t < bt)))))
-            w = ids[better]
-            best[w], tri[w], inst[w] = d[better], t, i
-            for c in range(3):
-                q[w, c] = np.broadcast_to(cq[c], d2.shape)[better, k]
-            u[w], v[w], region[w] = np.broadcast_to(cu, d2.shape)[better, k], np.broadcast_to(cv, d2.shape)[better, k], np.broadcast_to(cr, d2.shape)[better, k]
-
-    for i in order:
-        visit(np.asarray(maps[i], F), int(i), 0, np.nonzero(walk)[0])
-    out = np.zeros(n, R.CLOSEST_DTYPE)
-    out["q"], out["dist2"], out["u"], out["v"], out["triangle"], out["region"] = q, best, u, v, tri, region
-    return out, inst.astype(np.int32), tests
 
 
 def set_maps(n, seed):
@@ -291,3 +204,39 @@ def test_scaling_by_a_power_of_two_scales_the_answer_exactly(lobed_positions, k)
     with np.errstate(invalid="ignore"):
         assert np.array_equal((want["q"] * s).view(np.uint32), got["q"].view(np.uint32))
         assert np.array_equal((want["dist2"] * s * s).view(np.uint32), got["dist2"].view(np.uint32))
+
+
+# 4 ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["leaf_root", "one_branch", "wide_by_one"])
+def test_the_walk_with_counters_answers_like_the_brute_force(name):
+    """instance_point_ref.walk_counters over a hand-shaped tree and refit_ref.node_boxes: its own answer is the restatement's
+    triangle under every kind of map, a point that is not walked counts nothing, a walked one counts the root, two bounds a
+    branch entered and every triangle of a leaf entered; where every dist2 is 0 nothing is culled."""
+    import instance_point_cases as IC
+    import refit_ref
+    import tree_shapes as T
+    tree, vertex_data = T.build(name)
+    corners = np.ascontiguousarray(vertex_data[tree.triangle_vertices][:, :, :3])
+    positions = corners.reshape(-1)
+    boxes = refit_ref.node_boxes(tree, corners)
+    rng = np.random.default_rng(len(name))
+    leaves = tree.negative < 0
+    for kind in ("identity", "rotation_nonuniform", "mirror", "shear", "signed_permutation"):
+        M = IC.map_of(kind, rng, positions, 1.5).astype(F)
+        pts, _, _ = IC.world_points([positions], [0], M[None], 160, seed=3)
+        want, _ = IP.closest_over_instances([positions], [0], M[None], pts)
+        w = IP.walk_counters(tree, boxes, corners, M, pts)
+        assert np.array_equal(w["triangle"], want["triangle"]), (name, kind)
+        go = np.isfinite(pts["p"]).all(1) & (pts["max_dist2"] >= 0)
+        assert np.array_equal(w["traversals"], go.astype(np.int64)) and (w["node_visits"][~go] == 0).all()
+        assert (w["node_visits"][go] % 2 == 1).all() and (w["node_visits"] <= tree.node_count).all()
+        assert (w["leaf_visits"] <= leaves.sum()).all() and (w["triangle_tests"] <= len(corners)).all()
+        assert (w["triangle_tests"][want["triangle"] >= 0] >= 1).all()
+        if tree.node_count > 3:
+            assert w["triangle_tests"][go].mean() < 0.5 * len(corners), "the image-box cull skips something"
+        tied = pts.copy()
+        tied["p"] = pts["p"] * F(2.0 ** -100)
+        tied["max_dist2"] = np.where(pts["max_dist2"] > 0, F(np.inf), pts["max_dist2"])
+        z = IP.walk_counters(tree, boxes, corners, M * F(2.0 ** -100), tied)
+        assert (z["triangle"][go] == 0).all() and (z["triangle_tests"][go] == len(corners)).all()
+        assert (z["node_visits"][go] == tree.node_count).all() and (z["leaf_visits"][go] == leaves.sum()).all()
