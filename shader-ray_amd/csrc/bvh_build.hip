@@ -20,8 +20,18 @@
 //              order of a leaf's triangles (which decides ties between equal hit distances, fs:333-340), is the reference's
 // and the tree is renumbered from creation (breadth-first) order to the pre-order shray_host_export_tree gives.  All float
 // expressions keep the host builder's operand order (host/bvh.cpp; -ffp-contract=off, correctly rounded division), so the
-// tree, the boxes and the triangle order equal the host's bit for bit (tests/test_gpu_bvh_build.py).  Not reproduced: the order
-// in which the sequential min / max meets a +0 and a -0 of the same box plane (the keys put -0 below +0).
+// tree, the boxes and the triangle order equal the host's bit for bit (tests/test_gpu_bvh_build.py, and at the ties, range ends
+// and option edges tests/test_gpu_bvh_build_edges.py).
+//
+// Zeros of both signs.  The sequential std::min / std::max keep whichever of +0 and -0 they met first, the keys put -0 below +0:
+// the two would part if a min or a max ever saw both.  None does, because no finite input puts a -0 into one.  Every operand of
+// a min / max here is c - 1e-5f or c + 1e-5f (a corner's coordinate, or a barycentre's: box3d::add(point)), or a min / max of
+// such values (a triangle's, a bin's, a node's box).  In round-to-nearest c - 1e-5f is a zero only for c == 1e-5f and c + 1e-5f
+// only for c == -1e-5f, and x - x is +0; a c of either zero gives -+1e-5f; where the bump is absorbed (|c| >= 512 certainly)
+// c -+ 1e-5f == c is not zero.  (A barycentre may itself be -0; its box planes are -+1e-5f.)  So every zero on a box plane is
+// +0, dim()'s hi - lo is never (-0) - (+0) = -0 either, and fmaxf(0, x) equals std::max(0, x) for every x that occurs, NaN
+// included (both give 0).  tests/bvh_build_cases.py's `zeros` cases hold corners of +0, -0, +-1e-5f and +-2e-5f in every position;
+// in `zeros_on_planes` every node's low x and high y plane is such a +0 (tests/test_bvh_build_cases_reference.py checks the signs).
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/functional.hpp>

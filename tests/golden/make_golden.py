@@ -12,6 +12,10 @@ Writes, next to this script:
                       package generates (scenes.bunny_trisrc, scenes.small_obj_no_normals), with the SHA-256 of
                       the generated file under `input_sha256`; the bunny-class scene's arrays of more than 64
                       floats are stored as SHA-256 digests of their bits (`<name>.sha256`, `<name>.size`)
+  bvh_build_cases.ref.npz  the reference's dumps of the BVH-build edge cases (tests/bvh_build_cases.py: files written to a
+                      temporary directory, not committed), under the default build parameters and, for four of them,
+                      under each option set, one reference process per dump: per case the SHA-256 of each flattened
+                      array's bits, the arrays' sizes, the counts and the SHA-256 of the case's file
   lobed_528.oracle.npz  64x64 frames of the small trisrc scene rendered by the CPU oracle
                       (gold and glazed plaster) -- regression vectors for the GPU path;
                       they pin the oracle's output at the time of commit, not the reference
@@ -88,9 +92,17 @@ def dump_generated_reference(scene_path, out_npz, digest_above=None):
     np.savez_compressed(out_npz, **d)
 
 
+def dump_bvh_build_cases(pkg):
+    import tempfile
+    import bvh_build_cases
+    with tempfile.TemporaryDirectory() as directory:
+        bvh_build_cases.write_fixture(bvh_build_cases.CaseSet(pkg, directory))
+
+
 def main():
     pkg = load_package()
     subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "all"], check=True, stdout=subprocess.DEVNULL)
+    dump_bvh_build_cases(pkg)
 
     tri_path = os.path.join(HERE, "lobed_528.trisrc")
     pos, tri = pkg.scenes.lobed_sphere_mesh(12, 24, bumpiness=0.22, ears=True)
