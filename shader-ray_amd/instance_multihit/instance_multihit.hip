@@ -1,9 +1,8 @@
 // instance_multihit.hip -- include/shader_ray_instance_multihit.h: every crossing of a world-space ray with a set of placed
 // scenes, counted, the first K kept in order with their instances.
 //
-// One lane per ray in one-wave workgroups.  The wave walks the set's top level uniformly, as instance.hip's kernel does
-// (instance/top_level.h: the widened slab test, the untested root, near children first by the first live lane's signs, a
-// 32-word LDS stack read with readfirstlane); at a leaf the lanes whose rays enter its box move their rays into the
+// One lane per ray in one-wave workgroups.  The wave walks the set's top level uniformly (instance/top_level.h's
+// walk_top_level, with its widened slab test); at a leaf the lanes whose rays enter its box move their rays into the
 // instance's object space and each runs the all-hits walk of that scene (multihit/all_hits_walk.h) into its own K best,
 // which carry the instance index as a fifth field.  The cull limit of a lane is its tmax, or, in the form that is not asked
 // for counts, the K-th smallest t it holds: the same t_K that prunes the walks inside the scenes.
@@ -15,6 +14,7 @@
 
 #include "all_hits_walk.h"
 #include "client_internal.h"
+#include "enter_set.h"
 #include "first_k_query.h"
 #include "multihit_host.h"
 #include "packed_walk.h"
@@ -65,42 +65,23 @@ __global__ void __launch_bounds__(kBlock) instance_all_hits_kernel(SetWork w, co
     const float pmax = fmaxf(fabsf(P.x), fmaxf(fabsf(P.y), fabsf(P.z)));
     const unsigned long long first = __builtin_amdgcn_ballot_w64(traced);
     if (first) {
-        // near children first by the first live lane's direction signs (the walk's order affects its speed only)
-        const uint32_t signs = (uint32_t)__builtin_amdgcn_readlane((int)((D.x >= 0.0f ? 1u : 0u) | (D.y >= 0.0f ? 2u : 0u) |
-                                                                          (D.z >= 0.0f ? 4u : 0u)),
-                                                                    (int)__builtin_ctzll(first));
-        uint32_t node = 0;
-        int sp = 0;
-        for (;;) {
-            const float4 a = reinterpret_cast<const float4 *>(nodes)[2u * node];
-            const float4 b = reinterpret_cast<const float4 *>(nodes)[2u * node + 1u];
-            // The root is not tested: a set of one instance culls nothing, so its walks are the plain query's.  A lane's
-            // limit: nothing beyond tmax is accepted; nothing beyond t_K can enter the first k (a box that begins AT t_K
-            // is entered: enters_box keeps tn <= limit, and a lower instance wins a tie there)
-            const bool enters = traced && (node == 0u || enters_box(a, b, P, D, a.w * pmax, PRUNE ? best.tk : tmax));
-            if (__builtin_amdgcn_ballot_w64(enters)) {
-                const uint32_t link = __float_as_uint(b.w);
-                if (!(link & kLeafBit)) {
-                    const uint32_t left = link & 0x1fffffffu;
-                    const bool low_first = (signs >> (link >> 29)) & 1u;
-                    top[sp++] = low_first ? left + 1u : left;   // the far child waits (every lane writes the same word)
-                    node = low_first ? left : left + 1u;
-                    continue;
-                }
-                const int inst = (int)(link & ~kLeafBit);
-                const float4 *rec = records + 4u * (uint32_t)inst;
-                const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
-                const SceneView &sc = views[__float_as_uint(rec[3].x)];
+        const uint32_t signs = first_lane_signs(D, first);
+        walk_top_level(
+            nodes, top,
+            // A lane's limit: nothing beyond tmax is accepted; nothing beyond t_K can enter the first k (a box that begins
+            // AT t_K is entered: enters_box keeps tn <= limit, and a lower instance wins a tie there)
+            [&](uint32_t node, const float4 &a, const float4 &b) {
+                return traced && (node == 0u || enters_box(a, b, P, D, a.w * pmax, PRUNE ? best.tk : tmax));
+            },
+            [&](uint32_t link, uint32_t, unsigned long long) -> bool { return (signs >> (link >> 29)) & 1u; },
+            [&](int inst, bool enters) {
+                const SceneView &sc = leaf_view(records, views, inst);
                 if (enters) {
-                    const V3 Po = mk(object_row(r0, P, true), object_row(r1, P, true), object_row(r2, P, true));
-                    const V3 Do = mk(object_row(r0, D, false), object_row(r1, D, false), object_row(r2, D, false));
+                    V3 Po, Do;
+                    object_ray(records + 4u * (uint32_t)inst, P, D, Po, Do);
                     all_hits_walk<SLOTS, PRUNE, true>(sc, Po, Do, tmax, w.max_leaf_tests, inst, column, best, rc);
                 }
-            }
-            if (sp == 0)
-                break;
-            node = (uint32_t)__builtin_amdgcn_readfirstlane((int)top[--sp]);
-        }
+            });
     }
     if (live) {
         best.store(w.instances ? w.instances + index * (uint64_t)w.k : nullptr);
@@ -112,26 +93,6 @@ __global__ void __launch_bounds__(kBlock) instance_all_hits_kernel(SetWork w, co
 }
 
 constexpr Nouns kNouns = {"ray", "rays", "set", "hits", "max_hits", "instanced all-hits ray query"};
-
-// the set's arrays on its device, and the height of its tallest member tree (each member's read back once per scene)
-int enter_set(shray_instance_set *set, ShrayInstanceSetDevice *d, int *height)
-{
-    int rc = shrayi_instance_set_device_arrays(set, d);
-    if (rc)
-        return rc;
-    if ((rc = use_device(d->device)))
-        return rc;
-    *height = 0;
-    for (int32_t s = 0; s < d->scene_count; s++) {
-        ShrayQueryScene q;
-        int h = 0;
-        if ((rc = shrayi_scene_query_view(d->scenes[s], &q)) || (rc = check_walkable(q, 0)) || (rc = scene_tree_height(q, d->scenes[s], &h)) ||
-            (rc = check_walkable(q, h)))
-            return rc;
-        *height = h > *height ? h : *height;
-    }
-    return SHRAY_OK;
-}
 
 int trace_device(shray_instance_set *set, const shray_multihit_params *mp, const shray_ray *d_rays, int64_t count, shray_hit *d_hits,
                  int32_t *d_instances, int32_t *d_counts, hipStream_t stream, DeviceCounters *d_counters)

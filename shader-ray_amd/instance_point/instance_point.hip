@@ -1,8 +1,8 @@
 // instance_point.hip -- include/shader_ray_instance_point.h: the nearest surface point of a set of placed scenes to each
 // world-space point, and the instance it lies on.
 //
-// One lane per point in one-wave workgroups.  The wave walks the set's top level uniformly (instance/top_level.h's nodes, a
-// 32-word LDS stack read with readfirstlane, the untested root); a node is entered when any lane's box bound of its stored box
+// One lane per point in one-wave workgroups.  The wave walks the set's top level uniformly (instance/top_level.h's
+// walk_top_level); a node is entered when any lane's box bound of its stored box
 // is not above that lane's best dist2, the nearer child first by the first entering lane's bounds.  At a leaf the instance is
 // wave-uniform: its forward map's three rows and the member's SceneView come in by scalar loads, and the lanes whose bound
 // passes run the closest-point walk of that member's packed tree (point/point_walk.h's loop) with every box replaced by its
@@ -16,6 +16,7 @@
 
 #include "client_internal.h"
 #include "closest_on_triangle.h"
+#include "enter_set.h"
 #include "packed_walk.h"
 #include "shader_ray_instance_point.h"
 #include "top_level.h"
@@ -161,43 +162,31 @@ __global__ void __launch_bounds__(kBlock) instance_closest_kernel(SetWork w, con
     unsigned int visited = 0, leaves = 0, tests = 0, walks = 0;
 
     if (__builtin_amdgcn_ballot_w64(walk)) {
-        uint32_t node = 0;
-        int sp = 0;
-        for (;;) {
-            const float4 a = reinterpret_cast<const float4 *>(nodes)[2u * node];
-            const float4 b = reinterpret_cast<const float4 *>(nodes)[2u * node + 1u];
-            const float lo[3] = {a.x, a.y, a.z}, hi[3] = {b.x, b.y, b.z};
-            // The root is not tested: a set of one instance culls nothing, so its walks are the plain query's.  The stored box
-            // holds every fp32 world corner below it, so its bound is never above a pair's dist2; no ray-origin pad here.
-            const bool enters = walk && (node == 0u || !(box_bound(p, lo, hi) > best.dist2));
-            const unsigned long long entering = __builtin_amdgcn_ballot_w64(enters);
-            if (entering) {
-                const uint32_t link = __float_as_uint(b.w);
-                if (!(link & kLeafBit)) {
-                    // the nearer child first by the first entering lane's bounds (the walk's order affects its speed only)
-                    const uint32_t left = link & 0x1fffffffu;
-                    const float4 la = reinterpret_cast<const float4 *>(nodes)[2u * left], lb = reinterpret_cast<const float4 *>(nodes)[2u * left + 1u];
-                    const float4 ra = reinterpret_cast<const float4 *>(nodes)[2u * left + 2u], rb = reinterpret_cast<const float4 *>(nodes)[2u * left + 3u];
-                    const float llo[3] = {la.x, la.y, la.z}, lhi[3] = {lb.x, lb.y, lb.z}, rlo[3] = {ra.x, ra.y, ra.z}, rhi[3] = {rb.x, rb.y, rb.z};
-                    const int mine = box_bound(p, rlo, rhi) < box_bound(p, llo, lhi) ? 1 : 0;
-                    const bool right_first = __builtin_amdgcn_readlane(mine, (int)__builtin_ctzll(entering)) != 0;
-                    top[sp++] = right_first ? left : left + 1u;   // the farther child waits (every lane writes the same word)
-                    node = right_first ? left + 1u : left;
-                    continue;
-                }
-                const int inst = (int)(link & ~kLeafBit);
+        walk_top_level(
+            nodes, top,
+            // The stored box holds every fp32 world corner below it, so its bound is never above a pair's dist2; no
+            // ray-origin pad here.
+            [&](uint32_t node, const float4 &a, const float4 &b) {
+                const float lo[3] = {a.x, a.y, a.z}, hi[3] = {b.x, b.y, b.z};
+                return walk && (node == 0u || !(box_bound(p, lo, hi) > best.dist2));
+            },
+            // the nearer child first by the first entering lane's bounds (the walk's order affects its speed only)
+            [&](uint32_t, uint32_t left, unsigned long long entering) {
+                const float4 la = reinterpret_cast<const float4 *>(nodes)[2u * left], lb = reinterpret_cast<const float4 *>(nodes)[2u * left + 1u];
+                const float4 ra = reinterpret_cast<const float4 *>(nodes)[2u * left + 2u], rb = reinterpret_cast<const float4 *>(nodes)[2u * left + 3u];
+                const float llo[3] = {la.x, la.y, la.z}, lhi[3] = {lb.x, lb.y, lb.z}, rlo[3] = {ra.x, ra.y, ra.z}, rhi[3] = {rb.x, rb.y, rb.z};
+                const int mine = box_bound(p, rlo, rhi) < box_bound(p, llo, lhi) ? 1 : 0;
+                return __builtin_amdgcn_readlane(mine, (int)__builtin_ctzll(entering)) == 0;
+            },
+            [&](int inst, bool enters) {
                 const float4 *row = maps + 3u * (uint32_t)inst;
                 const float4 m[3] = {row[0], row[1], row[2]};
-                const SceneView &sc = views[__float_as_uint(records[4u * (uint32_t)inst + 3u].x)];
+                const SceneView &sc = leaf_view(records, views, inst);
                 if (enters) {
                     walks++;
                     instance_walk(sc, m, inst, p, column, best, visited, leaves, tests);
                 }
-            }
-            if (sp == 0)
-                break;
-            node = (uint32_t)__builtin_amdgcn_readfirstlane((int)top[--sp]);
-        }
+            });
     }
     if (live) {
         const bool hit = best.tri >= 0;
@@ -216,26 +205,6 @@ __global__ void __launch_bounds__(kBlock) instance_closest_kernel(SetWork w, con
             atomicAdd(&c->traversals, s3);
         }
     }
-}
-
-// the set's arrays on its device, and the height of its tallest member tree (each member's read back once per scene)
-int enter_set(shray_instance_set *set, ShrayInstanceSetDevice *d, int *height)
-{
-    int rc = shrayi_instance_set_device_arrays(set, d);
-    if (rc)
-        return rc;
-    if ((rc = use_device(d->device)))
-        return rc;
-    *height = 0;
-    for (int32_t s = 0; s < d->scene_count; s++) {
-        ShrayQueryScene q;
-        int h = 0;
-        if ((rc = shrayi_scene_query_view(d->scenes[s], &q)) || (rc = check_walkable(q, 0)) || (rc = scene_tree_height(q, d->scenes[s], &h)) ||
-            (rc = check_walkable(q, h)))
-            return rc;
-        *height = h > *height ? h : *height;
-    }
-    return SHRAY_OK;
 }
 
 int closest_device(shray_instance_set *set, const shray_point *d_points, int64_t count, shray_closest *d_out, int32_t *d_instances,
