@@ -21,6 +21,8 @@ WINDING_LIB = os.path.join(PKG_DIR, "libshray_winding.so")
 MULTIHIT_LIB = os.path.join(PKG_DIR, "libshray_multihit.so")
 INSTANCE_MULTIHIT_LIB = os.path.join(PKG_DIR, "libshray_instance_multihit.so")
 INSTANCE_POINT_LIB = os.path.join(PKG_DIR, "libshray_instance_point.so")
+# SHRAY_INSTANCE_NEAR_LIB selects an experiment build of the same library (the stack entry); unset in normal use
+INSTANCE_NEAR_LIB = os.environ.get("SHRAY_INSTANCE_NEAR_LIB") or os.path.join(PKG_DIR, "libshray_instance_near.so")
 # SHRAY_NEAR_LIB selects an experiment build of the same library (profiles/near_bench.py --ab); unset in normal use
 NEAR_LIB = os.environ.get("SHRAY_NEAR_LIB") or os.path.join(PKG_DIR, "libshray_near.so")
 OVERLAP_LIB = os.path.join(PKG_DIR, "libshray_overlap.so")
@@ -479,6 +481,16 @@ INSTANCE_POINT_SYMBOLS = [
                                                           C.POINTER(Counters)]),
 ]
 
+# include/shader_ray_instance_near.h -----------------------------------------------------------------------
+INSTANCE_NEAR_SYMBOLS = [
+    ("shray_near_triangles_instances_device", C.c_int, [C.c_void_p, C.POINTER(NearParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p]),
+    ("shray_near_triangles_instances", C.c_int, [C.c_void_p, C.POINTER(NearParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]),
+    ("shray_near_triangles_instances_counters", C.c_int, [C.c_void_p, C.POINTER(NearParams), C.c_void_p, C.c_int64, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
+]
+
 _host = None
 _hip = None
 _clients = {}   # path -> the loaded client library of libshray_hip.so
@@ -595,6 +607,11 @@ def load_instance_multihit():
 def load_instance_point():
     """Loads the instanced closest-point library (libshray_instance_point.so: depends on libshray_instance.so too)."""
     return _load_client(INSTANCE_POINT_LIB, INSTANCE_POINT_SYMBOLS)
+
+
+def load_instance_near():
+    """Loads the instanced within-radius library (libshray_instance_near.so: depends on libshray_instance.so too)."""
+    return _load_client(INSTANCE_NEAR_LIB, INSTANCE_NEAR_SYMBOLS)
 
 
 def check_dist(code: int):

@@ -1245,6 +1245,46 @@ class InstanceSet:
         N.check(N.load_instance_point().shray_closest_points_instances_device(
             self._handle, C.c_void_p(points_ptr), count, C.c_void_p(out_ptr), C.c_void_p(instances_ptr or None), C.c_void_p(stream_ptr)))
 
+    def triangles_within(self, points, max_near: int = 8, counts: bool = True, counters: bool = False):
+        """Instanced within-radius queries (include/shader_ray_instance_near.h): per world-space point the number of
+        (instance, triangle) pairs whose closest point lies within its max_dist2, measured on the instances' triangles mapped
+        to the world by the set's object-to-world floats, and the nearest `max_near` of them as shray_closest records, sorted
+        by (dist2, instance, triangle), the other slots miss records with instance -1.  `points` as for
+        Scene.triangles_within: host points take the blocking path and return (records: CLOSEST_DTYPE [n, max_near],
+        instances: int32 [n, max_near], counts: int32 [n]); a float32 [n, 3] / [n, 4] GPU tensor on the set's device takes the
+        device path on the current torch stream and returns (int32 [n, max_near, 8] tensor of shray_closest records, int32
+        [n, max_near] tensor, int32 [n] tensor).  counts=False returns None for the counts and lets the walks skip what cannot
+        reach the nearest `max_near` (the same records); max_near = 0 returns None for the records and instances.
+        counters=True (host points only) also returns the counters of the walk that prunes only by max_dist2, summed over a
+        point's walks."""
+        lib = N.load_instance_near()
+        return _first_k(self._handle, (lib.shray_near_triangles_instances_device, lib.shray_near_triangles_instances,
+                                       lib.shray_near_triangles_instances_counters),
+                        near_params(max_near), max_near, "max_near", points, "points", self._device_points, _host_points, CLOSEST_DTYPE,
+                        (8,), True, counts, counters)
+
+    def _device_points(self, points):
+        """a GPU point tensor on the set's device as a contiguous shray_point tensor (Scene._device_points's forms)"""
+        if points.device.index != self.device:
+            raise ValueError(f"points are on {points.device}, the set on cuda:{self.device}")
+        return self._scenes[0]._device_points(points)
+
+    def triangles_within_into(self, points_ptr: int, count: int, out_ptr: int, instances_ptr: int = 0, counts_ptr: int = 0,
+                              max_near: int = 8, stream_ptr: int = 0):
+        """Asynchronous instanced within-radius queries on device memory of the set's device
+        (shray_near_triangles_instances_device): `count` shray_point records at `points_ptr` -> count * max_near shray_closest
+        records at `out_ptr` (0 iff max_near is 0), unless `instances_ptr` is 0 count * max_near int32 instance indices there,
+        and unless `counts_ptr` is 0 `count` int32 near counts there, on a HIP stream (`stream_ptr`)."""
+        np_ = near_params(max_near)
+        N.check(N.load_instance_near().shray_near_triangles_instances_device(
+            self._handle, C.byref(np_), C.c_void_p(points_ptr), count, C.c_void_p(out_ptr or None), C.c_void_p(instances_ptr or None),
+            C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+
+    def near_counts(self, points):
+        """How many (instance, triangle) pairs lie within each world point's max_dist2 (triangles_within with max_near = 0):
+        int32 [n], numpy for host points, a tensor for GPU points."""
+        return self.triangles_within(points, max_near=0, counts=True)[2]
+
     def close(self):
         if getattr(self, "_handle", None):
             self._lib.shray_instance_set_destroy(self._handle)
