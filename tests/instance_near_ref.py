@@ -6,8 +6,9 @@ scene) by instance_point_ref.split_index.  The merged scene's key (dist2, merged
 triangle) by construction.
 
 restated_walk is the kernel's walk in numpy and plain python, one point at a time, over a median-split tree per instance, with
-every decision the kernel takes replaceable (the two skips, the tie rule, the slot the reach is read from, what n counts), so
-that tests/test_instance_near_reference.py can show which input catches which mistake.  walk_counters is the counting form's
+every decision the kernel takes replaceable (the two skips, the tie rule, the slot the reach is read from, what n counts, the
+membership test against max_dist2), so that tests/test_instance_near_reference.py and
+tests/test_instance_near_scale_reference.py can show which input catches which mistake.  walk_counters is the counting form's
 walk of ONE instance, one point at a time, over a refit_ref.TreeArrays: its node visits, leaf visits and triangle tests, and
 whether the point walks the instance at all (the top level's stored box, when one is given).
 """
@@ -42,6 +43,11 @@ def key_instance_first(d, i, t):
     return (d, i, t)
 
 
+def at_or_under(d, max_dist2):
+    """the kernel's membership: dist2 <= max_dist2, inclusive (false for a NaN on either side)"""
+    return d <= max_dist2
+
+
 def prepare(corners, maps, points, top_boxes=None):
     """what restated_walk needs per instance, for all points at once: (median tree of the object corners, image-box bounds
     [n, nodes], dist2 of every pair [n, T], world corners, top-level box bounds [n] or None)"""
@@ -69,11 +75,11 @@ def prepare(corners, maps, points, top_boxes=None):
 
 
 def restated_walk(corners, maps, points, order, k, counts, *, node_skip=above, top_boxes=None, top_skip=above,
-                  key=key_instance_first, reach_slot=-1, count_kept_only=False, prepared=None):
+                  key=key_instance_first, reach_slot=-1, count_kept_only=False, within=at_or_under, prepared=None):
     """The kernel's walk, one point at a time: the instances in `order`; with `top_boxes` (one (lo, hi) per instance: the top
     level as a list of its leaves) an instance is entered only when the bound of its box is not above the point's reach; in an
     instance the median tree of the object corners, a node skipped only when the bound of its IMAGE box is above the reach,
-    the nearer child first, every triangle of a visited leaf mapped and tested, n counted for every pair within max_dist2 and
+    the nearer child first, every triangle of a visited leaf mapped and tested, n counted for every pair `within` max_dist2 and
     the pair's key inserted into the sorted K best.  The reach is max_dist2 with `counts` (or k == 0), else the dist2 of the
     held slot k + reach_slot (0-based: the K-th smallest), max_dist2 while that slot is empty.  `corners` is one [t, 3, 3]
     array for every instance or a list with one per instance.  The keyword arguments replace one decision each (the tests'
@@ -121,7 +127,7 @@ def restated_walk(corners, maps, points, order, k, counts, *, node_skip=above, t
                 for t in ids:
                     tests += 1
                     d = d2[j, t]
-                    if not d <= mdj:
+                    if not within(d, mdj):
                         continue
                     kk = key(d, int(i), int(t))
                     kept = k > 0 and (len(held) < k or kk < held[-1])
