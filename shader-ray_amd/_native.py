@@ -26,6 +26,7 @@ INSTANCE_NEAR_LIB = os.environ.get("SHRAY_INSTANCE_NEAR_LIB") or os.path.join(PK
 # SHRAY_NEAR_LIB selects an experiment build of the same library (profiles/near_bench.py --ab); unset in normal use
 NEAR_LIB = os.environ.get("SHRAY_NEAR_LIB") or os.path.join(PKG_DIR, "libshray_near.so")
 OVERLAP_LIB = os.path.join(PKG_DIR, "libshray_overlap.so")
+INSTANCE_OVERLAP_LIB = os.path.join(PKG_DIR, "libshray_instance_overlap.so")
 INTERSECT_LIB = os.path.join(PKG_DIR, "libshray_intersect.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
 HIP_LIB = os.environ.get("SHRAY_HIP_LIB") or os.path.join(PKG_DIR, "libshray_hip.so")
@@ -491,6 +492,16 @@ INSTANCE_NEAR_SYMBOLS = [
                                                           C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
 ]
 
+# include/shader_ray_instance_overlap.h --------------------------------------------------------------------
+INSTANCE_OVERLAP_SYMBOLS = [
+    ("shray_overlap_triangles_instances_device", C.c_int, [C.c_void_p, C.POINTER(OverlapParams), C.c_void_p, C.c_int64, C.c_void_p,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("shray_overlap_triangles_instances", C.c_int, [C.c_void_p, C.POINTER(OverlapParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p]),
+    ("shray_overlap_triangles_instances_counters", C.c_int, [C.c_void_p, C.POINTER(OverlapParams), C.c_void_p, C.c_int64, C.c_void_p,
+                                                             C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
+]
+
 _host = None
 _hip = None
 _clients = {}   # path -> the loaded client library of libshray_hip.so
@@ -612,6 +623,11 @@ def load_instance_point():
 def load_instance_near():
     """Loads the instanced within-radius library (libshray_instance_near.so: depends on libshray_instance.so too)."""
     return _load_client(INSTANCE_NEAR_LIB, INSTANCE_NEAR_SYMBOLS)
+
+
+def load_instance_overlap():
+    """Loads the instanced box-overlap library (libshray_instance_overlap.so: depends on libshray_instance.so too)."""
+    return _load_client(INSTANCE_OVERLAP_LIB, INSTANCE_OVERLAP_SYMBOLS)
 
 
 def check_dist(code: int):

@@ -1,5 +1,5 @@
-// top_level.h -- the walk of an instance set's top level and what its four callers share (instance.hip: closest and any hit;
-// instance_multihit/: all hits; instance_point/: closest points; instance_near/: within-radius).  walk_top_level
+// top_level.h -- the walk of an instance set's top level and what its five callers share (instance.hip: closest and any hit;
+// instance_multihit/: all hits; instance_point/: closest points; instance_near/: within-radius; instance_overlap/: boxes).  walk_top_level
 // is the only loop over TopNodes in device code; DESIGN.md sections 10, 16 and 20 argue it.  Beside it: the node and record
 // layout, a lane's widened slab test, the object ray (include/shader_ray_instance.h), a leaf's SceneView, and the accessors
 // through which another library reads a set's device arrays and forward maps.  Internal to the libraries; no kernel here.
@@ -139,7 +139,7 @@ struct ShrayInstanceSetDevice {
 // Not in the header: for libshray_instance_multihit.so.  Host-only; waits for nothing and touches no device.
 extern "C" int shrayi_instance_set_device_arrays(const shray_instance_set *set, ShrayInstanceSetDevice *out);
 
-// Not in the header: for libshray_instance_point.so and libshray_instance_near.so.  The set's current object_to_world floats on its device, float
+// Not in the header: for libshray_instance_point.so, libshray_instance_near.so and libshray_instance_overlap.so.  The set's current object_to_world floats on its device, float
 // [count][12], the very floats it was created or last updated with, for a launch enqueued on `hip_stream` after this call.
 // After a host update (and on first use) the upload is staged on that stream; after a device update the copy is the one
 // that update's commit wrote, in stream order.  Host-only; makes the set's device current and waits for nothing.

@@ -796,6 +796,16 @@ def overlap_params(max_triangles: int = 8, any_only: bool = False) -> N.OverlapP
     return op
 
 
+def _set_overlap_params(max_triangles: int = 8, any_only: bool = False) -> N.OverlapParams:
+    """shray_overlap_params for the instanced query, filled here: libshray_instance_overlap.so does not need libshray_overlap.so"""
+    op = N.OverlapParams()
+    op.struct_size = C.sizeof(N.OverlapParams)
+    op.max_triangles = max_triangles
+    op.flags = N.OVERLAP_ANY if any_only else 0
+    op.reserved = 0
+    return op
+
+
 def intersect_params(max_triangles: int = 8, any_only: bool = False, skip_shared: bool = False) -> N.IntersectParams:
     op = N.IntersectParams()
     N.load_intersect().shray_intersect_params_init(C.byref(op))
@@ -1284,6 +1294,59 @@ class InstanceSet:
         """How many (instance, triangle) pairs lie within each world point's max_dist2 (triangles_within with max_near = 0):
         int32 [n], numpy for host points, a tensor for GPU points."""
         return self.triangles_within(points, max_near=0, counts=True)[2]
+
+    def triangles_in_boxes(self, boxes, max_triangles: int = 8, counts: bool = True, counters: bool = False, any_only: bool = False):
+        """Instanced box-overlap queries (include/shader_ray_instance_overlap.h): per axis-aligned world box the number of
+        (instance, triangle) pairs that touch it, tested on the instances' triangles mapped to the world by the set's
+        object-to-world floats, and the `max_triangles` smallest of them in (instance, triangle) order, the other slots
+        SHRAY_HIT_MISS (-1) with instance -1.  `boxes` as for Scene.triangles_in_boxes: host boxes take the blocking path and
+        return (indices: int32 [n, max_triangles], instances: int32 [n, max_triangles], counts: int32 [n]); a float32 [n, 6] /
+        [n, 8] GPU tensor on the set's device takes the device path on the current torch stream and returns tensors of the
+        same shapes.  counts=False returns None for the counts and lets a box that holds `max_triangles` pairs skip the
+        instances above them (the same indices); max_triangles = 0 returns None for the indices and instances.  any_only=True
+        (with max_triangles = 0) sets SHRAY_OVERLAP_ANY: the count is 1 or 0 and a box stops at its first touching pair.
+        counters=True (host boxes only) also returns the counters of the walk that does not prune, summed over a box's walks."""
+        lib = N.load_instance_overlap()
+        return _first_k(self._handle, (lib.shray_overlap_triangles_instances_device, lib.shray_overlap_triangles_instances,
+                                       lib.shray_overlap_triangles_instances_counters),
+                        _set_overlap_params(max_triangles, any_only), max_triangles, "max_triangles", boxes, "boxes", self._device_boxes,
+                        _host_boxes, np.int32, (), True, counts, counters)
+
+    def _device_boxes(self, boxes):
+        """a GPU box tensor on the set's device as a contiguous shray_box tensor (Scene._device_boxes's forms)"""
+        if boxes.device.index != self.device:
+            raise ValueError(f"boxes are on {boxes.device}, the set on cuda:{self.device}")
+        return self._scenes[0]._device_boxes(boxes)
+
+    def triangles_in_boxes_into(self, boxes_ptr: int, count: int, out_ptr: int, instances_ptr: int = 0, counts_ptr: int = 0,
+                                max_triangles: int = 8, any_only: bool = False, stream_ptr: int = 0):
+        """Asynchronous instanced box-overlap queries on device memory of the set's device
+        (shray_overlap_triangles_instances_device): `count` shray_box records at `boxes_ptr` -> count * max_triangles int32
+        triangle indices at `out_ptr` (0 iff max_triangles is 0), unless `instances_ptr` is 0 count * max_triangles int32
+        instance indices there, and unless `counts_ptr` is 0 `count` int32 counts there, on a HIP stream (`stream_ptr`)."""
+        op = _set_overlap_params(max_triangles, any_only)
+        N.check(N.load_instance_overlap().shray_overlap_triangles_instances_device(
+            self._handle, C.byref(op), C.c_void_p(boxes_ptr), count, C.c_void_p(out_ptr or None), C.c_void_p(instances_ptr or None),
+            C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+
+    def box_counts(self, boxes):
+        """How many (instance, triangle) pairs touch each world box (triangles_in_boxes with max_triangles = 0): int32 [n],
+        numpy for host boxes, a tensor for GPU boxes."""
+        return self.triangles_in_boxes(boxes, max_triangles=0, counts=True)[2]
+
+    def boxes_touched(self, boxes):
+        """Whether any triangle of any instance touches each world box (SHRAY_OVERLAP_ANY: a box stops at its first pair):
+        bool [n], numpy for host boxes, a tensor for GPU boxes."""
+        return self.triangles_in_boxes(boxes, max_triangles=0, counts=True, any_only=True)[2] != 0
+
+    def surface_voxels(self, origin, cell, dims, device=None):
+        """The occupancy grid of the placed surfaces: bool [nx, ny, nz], voxel (i, j, k) set iff a triangle of an instance
+        touches the box of Scene.surface_voxels (voxel_boxes: the same planes, shared bit for bit by neighbours).  device=None
+        builds the boxes with numpy and takes the host path; a torch device (the set's) builds them there and returns a
+        tensor.  The query is boxes_touched."""
+        boxes = voxel_boxes(origin, cell, dims, device)
+        nx, ny, nz = (int(d) for d in dims)
+        return self.boxes_touched(boxes).reshape(nx, ny, nz)
 
     def close(self):
         if getattr(self, "_handle", None):
