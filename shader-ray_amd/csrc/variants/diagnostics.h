@@ -13,6 +13,10 @@
 // SHRAY_DIAG_UNIFORM (with SHRAY_DIAGNOSTICS; profiles/uniform_visit_histogram.py, round 6): the eight tallies count the node stage's
 // wave-visits -- {all, wave-uniform (every walking lane at one record), of those: every lane enters, no lane enters, mixed; visits
 // with two distinct records, with three or four; walking lanes in all visits} (variants/diag_uniform_visit.inc).
+// SHRAY_DIAG_UNIFORM_ORIGIN (with both; uniform_visit_histogram.py --origin, round 8): the last three tallies are instead {no-lane-enters
+// uniform visits directly after a uniform every-lane-enters-a-branch turn of the same stage call: within one group of
+// SHRAY_NODE_TURNS turns (bits 0-31), across the exit tests (bits 32-63); such visits at one remove or more; uniform
+// every-lane-enters visits at a leaf's record}.
 #if defined(SHRAY_DIAGNOSTICS) && (defined(SHRAY_DIAG_KHIST) || defined(SHRAY_DIAG_UNIFORM))
 #ifndef SHRAY_DIAG_KHIST_FROM
 #define SHRAY_DIAG_KHIST_FROM 32

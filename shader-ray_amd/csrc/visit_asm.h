@@ -46,6 +46,12 @@ namespace shray {
 #ifndef SHRAY_VISIT_RUNS
 #define SHRAY_VISIT_RUNS 1
 #endif
+// (-DSHRAY_VISIT_POPS=0, an A/B build: the uniform tail of round 6 -- only "every lane enters a branch" has a path of its own;
+//  =1, what ships: one path per uniform outcome, every pop through LDS; =2, an A/B build: a run's pushed word mirrored in a scalar
+//  register as well -- its timings do not separate from =1's, profiles/EXPERIMENTS.md R8.1)
+#ifndef SHRAY_VISIT_POPS
+#define SHRAY_VISIT_POPS 1
+#endif
 
 // the six products, the decision (see the file's header), and the way out for a turn the statement does not make
 #define SHRAY_VISIT_DECIDE                                                                                                       \
@@ -89,6 +95,95 @@ namespace shray {
     "vk" #K "_%=:\n\t"                                                                                                          \
     "v_add_u32_e32 %[L], -1, %[L]\n"                                                                                            \
     "vu" #K "_%=:\n\t"
+#if SHRAY_VISIT_POPS >= 1
+// ONE PATH PER UNIFORM OUTCOME (round 8, R8.1).  96 % of the uniform turns end with one decision in every lane; each of the three
+// such outcomes has a tail of its own, and only the mixed 4 % takes the general tail (vt/vb/vp):
+//   * every lane enters a branch: the run's push, as above;
+//   * NO lane enters (40 % of the uniform turns, 24 % of all wave-visits): the pop alone -- no leaf test, no moves of the
+//     children's words into lanes' registers, no mask algebra, no push under an empty mask;
+//   * every lane enters a leaf: the park alone, and the turn ends with an empty walking mask.
+// THE MIRROR (SHRAY_VISIT_POPS >= 2; built, bit-identical, its timings not separated from value 1's: off).  69 % of the
+// no-lane-enters uniform turns directly follow a run's push (profiles/r08/uniform_visits_by_origin.txt).  A run's push turn
+// keeps the pushed word in sM and sets the run state sKU to 2 ("in a run, and the top of every walking lane's stack is sM")
+// instead of 1.  If the NEXT turn is uniform and no lane enters, the pop is
+// `top -= one entry; node = sM; sF = (sM << 3) + the run's octant offset` and the wave stays in a run (sKU = 1): no LDS read, no
+// test against the stack's base (the entry exists), no wait, and the next head does not find out again that the lanes agree.
+// The invariant that makes sM every walking lane's stack top:
+//   - within one call of the statement the walking mask only loses lanes;
+//   - a run's push is made by EVERY walking lane, each lane writing the same word, s71, to its own stack;
+//   - sKU is 2 only between that push and the decision of the turn directly after it: every other way through a turn leaves it
+//     0 or 1 (the vector path is entered with sKU == 0 only; the park, the LDS pop and the general tail set 0; the mirrored pop
+//     sets 1), vslow / vcap / vdone leave the statement, which starts with sKU = 0, and the exit tests between turn 3 and turn 0
+//     lower 2 to 1: the run state may cross them (as sF does), the mirror's validity never does.
+// sM is written by s_mov and read by v_mov / s_lshl: a scalar-ALU-written scalar register, no wait states (the two-state rule
+// is for VALU-written ones: sF after v_readfirstlane in the head).
+#if SHRAY_VISIT_POPS >= 2
+#define SHRAY_VISIT_RUN_MARK                                                                                                     \
+    "s_mov_b32 %[sM], s71\n\t"                              /* the mirror: what every walking lane has just pushed */             \
+    "s_mov_b32 %[sKU], 2\n\t"
+#define SHRAY_VISIT_MIRROR_TEST(K)                                                                                               \
+    "s_cmp_eq_u32 %[sKU], 2\n\t"                            /* the turn directly after a run's push */                            \
+    "s_cbranch_scc1 vq" #K "_%=\n\t"
+#define SHRAY_VISIT_MIRROR_POP(K)                                                                                                \
+    "vq" #K "_%=:\n\t"                                                                                                          \
+    "v_add_u32_e32 %[T], %[down], %[T]\n\t"                                                                                     \
+    "v_mov_b32_e32 %[N], %[sM]\n\t"                                                                                             \
+    "s_lshl_b32 %[sF], %[sM], 3\n\t"                                                                                            \
+    "s_add_u32 %[sF], %[sF], %[sOCT]\n\t"                                                                                       \
+    "s_mov_b32 %[sKU], 1\n\t"                               /* still in a run; the mirror is spent */                             \
+    "s_branch ve" #K "_%=\n"
+#define SHRAY_VISIT_MIRROR_EXIT "s_min_u32 %[sKU], %[sKU], 1\n\t"
+#else
+#define SHRAY_VISIT_RUN_MARK "s_mov_b32 %[sKU], 1\n\t"
+#define SHRAY_VISIT_MIRROR_TEST(K)
+#define SHRAY_VISIT_MIRROR_POP(K)
+#define SHRAY_VISIT_MIRROR_EXIT
+#endif
+#define SHRAY_VISIT_UNIFORM_TAIL(K)                                                                                              \
+    SHRAY_VISIT_DECIDE                                                                                                           \
+    "s_cmp_eq_u64 %[sE], exec\n\t"                          /* every walking lane enters ... */                                   \
+    "s_cbranch_scc0 vn" #K "_%=\n\t"                                                                                            \
+    "s_bitcmp1_b32 s71, 31\n\t"                             /* ... a branch's record (b without the leaf flag) */                 \
+    "s_cbranch_scc1 vl" #K "_%=\n\t"                                                                                            \
+    "v_mov_b32_e32 v9, s71\n\t"                             /* the run goes on: push the other child, go to the first */          \
+    "ds_write_b32 %[T], v9\n\t"                                                                                                 \
+    "v_add_u32_e32 %[T], %[up], %[T]\n\t"                                                                                       \
+    "v_mov_b32_e32 %[N], s70\n\t"                                                                                               \
+    "s_lshl_b32 %[sF], s70, 3\n\t"                          /* (the shift drops the axis bits of the child's name) */             \
+    "s_add_u32 %[sF], %[sF], %[sOCT]\n\t"                                                                                       \
+    SHRAY_VISIT_RUN_MARK                                                                                                         \
+    "s_branch ve" #K "_%=\n"                                                                                                    \
+    "vn" #K "_%=:\n\t"                                                                                                          \
+    "s_cmp_eq_u64 %[sE], 0\n\t"                             /* no walking lane enters: the pop alone */                           \
+    "s_cbranch_scc0 vm" #K "_%=\n\t"                                                                                            \
+    SHRAY_VISIT_MIRROR_TEST(K)                                                                                                   \
+    "s_mov_b32 %[sKU], 0\n\t"                                                                                                   \
+    "v_cmpx_ne_u32_e32 %[T], %[B]\n\t"                      /* lanes whose stacks are empty have ended */                         \
+    "v_add_u32_e32 %[T], %[down], %[T]\n\t"                                                                                     \
+    "ds_read_b32 %[N], %[T]\n\t"                                                                                                \
+    "s_mov_b64 %[sW], exec\n\t"                                                                                                 \
+    "s_cbranch_execz vg_%=\n\t"                                                                                                 \
+    "s_branch ve" #K "_%=\n"                                                                                                    \
+    SHRAY_VISIT_MIRROR_POP(K)                                                                                                    \
+    "vl" #K "_%=:\n\t"                                      /* every walking lane enters this leaf: the park alone */             \
+    "s_cmp_eq_u32 s71, 0x80000000\n\t"                      /* a leaf without triangles: the compiler's visit */                  \
+    "s_cbranch_scc1 vslow_%=\n\t"                                                                                               \
+    "v_min3_f32 v4, v4, v5, v7\n\t"                         /* r1~ */                                                             \
+    "v_min_f32_e32 v4, 0x4cbebc20, v4\n\t"                                                                                      \
+    "v_mul_f32_e32 %[LR1], 0x3f800008, v4\n\t"                                                                                  \
+    "v_mul_f32_e32 %[LR0], 0x3f7ffff0, v2\n\t"                                                                                  \
+    "v_mov_b32_e32 %[LF], s70\n\t"                                                                                              \
+    "v_mov_b32_e32 %[LC], s71\n\t"                                                                                              \
+    "s_or_b64 %[sP], %[sP], exec\n\t"                                                                                           \
+    "s_mov_b64 %[sW], 0\n\t"                                /* nobody walks on */                                                 \
+    "s_branch vg_%=\n"                                                                                                          \
+    "vm" #K "_%=:\n\t"                                                                                                          \
+    "s_mov_b32 %[sKU], 0\n\t"                                                                                                   \
+    "v_mov_b32_e32 v8, s70\n\t"                                                                                                 \
+    "v_mov_b32_e32 v9, s71\n\t"                                                                                                 \
+    "s_branch vt" #K "_%=\n"
+#else
+#define SHRAY_VISIT_MIRROR_EXIT
 #define SHRAY_VISIT_UNIFORM_TAIL(K)                                                                                              \
     "s_mov_b32 %[sKU], 0\n\t"                                                                                                   \
     SHRAY_VISIT_DECIDE                                                                                                           \
@@ -108,7 +203,9 @@ namespace shray {
     "v_mov_b32_e32 v8, s70\n\t"                                                                                                 \
     "v_mov_b32_e32 v9, s71\n\t"                                                                                                 \
     "s_branch vt" #K "_%=\n"
+#endif
 #elif SHRAY_VISIT_SCALAR
+#define SHRAY_VISIT_MIRROR_EXIT
 #define SHRAY_VISIT_HEAD(K)                                                                                                      \
     "s_waitcnt lgkmcnt(0)\n\t"                              /* the node the last turn took off the stack */                       \
     "v_lshl_add_u32 %[A], %[N], 3, %[OCT]\n\t"              /* node_address(): (name << 3) + octant */                            \
@@ -122,6 +219,7 @@ namespace shray {
     "v_mov_b32_e32 v9, s71\n\t"                                                                                                 \
     "s_branch vj" #K "_%=\n"
 #else
+#define SHRAY_VISIT_MIRROR_EXIT
 #define SHRAY_VISIT_HEAD(K)                                                                                                      \
     "s_waitcnt lgkmcnt(0)\n\t"                                                                                                  \
     "v_lshl_add_u32 %[A], %[N], 3, %[OCT]\n\t"                                                                                  \
@@ -230,6 +328,12 @@ __device__ __forceinline__ void inner_stage_scheduled(const SceneView &sc, const
     lds_word *top = (lds_word *)t.top, *const base = (lds_word *)stack;
     for (;;) {
         uint32_t reason, first, address, in_a_run, run_octant;
+#if SHRAY_VISIT_SCALAR && SHRAY_VISIT_RUNS && SHRAY_VISIT_POPS >= 2
+        uint32_t mirror;   // sM: the word a run's push turn has just pushed (valid while sKU == 2)
+#define SHRAY_VISIT_MIRROR_OPERAND , [sM] "=&s"(mirror)
+#else
+#define SHRAY_VISIT_MIRROR_OPERAND
+#endif
         unsigned long long walking, parked, walked_in, entered, mask, leaves, saved;
         asm volatile(
             "s_mov_b64 %[saved], exec\n\t"
@@ -244,6 +348,7 @@ __device__ __forceinline__ void inner_stage_scheduled(const SceneView &sc, const
             SHRAY_VISIT_TURN(0) SHRAY_VISIT_TURN(1) SHRAY_VISIT_TURN(2) SHRAY_VISIT_TURN(3)
             "\nvg_%=:\n\t"
             "s_mov_b64 exec, %[saved]\n\t"
+            SHRAY_VISIT_MIRROR_EXIT                             // (the mirror never crosses the exit tests; the run state may)
             "v_cmp_gt_i32_e32 vcc, 0, %[L]\n\t"                 // fs:426-438, once per four visits (lane_apply_cap)
             "s_cbranch_vccnz vcap_%=\n\t"
             "s_cmp_eq_u64 %[sW], 0\n\t"
@@ -271,7 +376,7 @@ __device__ __forceinline__ void inner_stage_scheduled(const SceneView &sc, const
             : [N] "+v"(t.node), [T] "+v"(top), [L] "+v"(t.left), [ST] "+v"(state), [LF] "+v"(t.leaf_first), [LC] "+v"(t.leaf_count),
               [LR0] "+v"(t.leaf_r0), [LR1] "+v"(t.leaf_r1), [A] "=&v"(address), [sW] "=&s"(walking), [sP] "=&s"(parked),
               [sW0] "=&s"(walked_in), [sE] "=&s"(entered), [sT] "=&s"(mask), [sL] "=&s"(leaves), [saved] "=&s"(saved),
-              [sF] "=&s"(first), [reason] "=&s"(reason), [sKU] "=&s"(in_a_run), [sOCT] "=&s"(run_octant)
+              [sF] "=&s"(first), [reason] "=&s"(reason), [sKU] "=&s"(in_a_run), [sOCT] "=&s"(run_octant) SHRAY_VISIT_MIRROR_OPERAND
             : [Px] "v"(t.P.x), [Py] "v"(t.P.y), [Pz] "v"(t.P.z), [Yx] "v"(t.Y.x), [Yy] "v"(t.Y.y), [Yz] "v"(t.Y.z), [OCT] "v"(t.octant),
               [HT] "v"(t.hit.t), [B] "v"(base), [base] "s"(sc.packed_nodes), [sDIV] "s"(t.divide_mask), [keep] "s"(keep_walking),
               [up] "i"((unsigned int)(4 * BLOCK)), [down] "i"((unsigned int)(-4 * BLOCK))

@@ -408,6 +408,10 @@ template <bool COUNT, int BLOCK>
 __device__ __forceinline__ void inner_stage(const SceneView &sc, const FrameView &fr, LaneTraversal &t, int &state,
                                             uint32_t *stack, RayCounters &rc, int keep_walking, bool others_waiting SHRAY_DIAG_PARAM)
 {
+#if defined(SHRAY_DIAGNOSTICS) && defined(SHRAY_DIAG_UNIFORM) && defined(SHRAY_DIAG_UNIFORM_ORIGIN)
+    int diag_chain = 0;          // variants/diag_uniform_visit.inc: the run pushes of this stage call still on top of the stacks
+    bool diag_popped = false;    // ... and whether one has been popped since the last of them
+#endif
     for (;;) {
         if (!wave_ballot(state == LT_WALK))
             return;
