@@ -28,6 +28,7 @@ NEAR_LIB = os.environ.get("SHRAY_NEAR_LIB") or os.path.join(PKG_DIR, "libshray_n
 OVERLAP_LIB = os.path.join(PKG_DIR, "libshray_overlap.so")
 INSTANCE_OVERLAP_LIB = os.path.join(PKG_DIR, "libshray_instance_overlap.so")
 INTERSECT_LIB = os.path.join(PKG_DIR, "libshray_intersect.so")
+INSTANCE_INTERSECT_LIB = os.path.join(PKG_DIR, "libshray_instance_intersect.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
 HIP_LIB = os.environ.get("SHRAY_HIP_LIB") or os.path.join(PKG_DIR, "libshray_hip.so")
 
@@ -502,6 +503,22 @@ INSTANCE_OVERLAP_SYMBOLS = [
                                                              C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
 ]
 
+# include/shader_ray_instance_intersect.h ------------------------------------------------------------------
+INTERSECT_SKIP_OWN_INSTANCE = 4   # the instance form only
+
+INSTANCE_INTERSECT_SYMBOLS = [
+    ("shray_intersect_triangles_instances_device", C.c_int, [C.c_void_p, C.POINTER(IntersectParams), C.c_void_p, C.c_int64, C.c_void_p,
+                                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("shray_intersect_triangles_instances", C.c_int, [C.c_void_p, C.POINTER(IntersectParams), C.c_void_p, C.c_int64, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p]),
+    ("shray_intersect_triangles_instances_counters", C.c_int, [C.c_void_p, C.POINTER(IntersectParams), C.c_void_p, C.c_int64, C.c_void_p,
+                                                               C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
+    ("shray_intersect_instance_device", C.c_int, [C.c_void_p, C.POINTER(IntersectParams), C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("shray_intersect_instance", C.c_int, [C.c_void_p, C.POINTER(IntersectParams), C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+]
+
 _host = None
 _hip = None
 _clients = {}   # path -> the loaded client library of libshray_hip.so
@@ -628,6 +645,11 @@ def load_instance_near():
 def load_instance_overlap():
     """Loads the instanced box-overlap library (libshray_instance_overlap.so: depends on libshray_instance.so too)."""
     return _load_client(INSTANCE_OVERLAP_LIB, INSTANCE_OVERLAP_SYMBOLS)
+
+
+def load_instance_intersect():
+    """Loads the instanced triangle-intersection library (libshray_instance_intersect.so: depends on libshray_instance.so too)."""
+    return _load_client(INSTANCE_INTERSECT_LIB, INSTANCE_INTERSECT_SYMBOLS)
 
 
 def check_dist(code: int):

@@ -1,4 +1,4 @@
-// enter_set.h -- how the instanced queries outside libshray_instance.so (instance_multihit/, instance_point/, instance_near/, instance_overlap/) enter a set on
+// enter_set.h -- how the instanced queries outside libshray_instance.so (instance_multihit/, instance_point/, instance_near/, instance_overlap/, instance_intersect/) enter a set on
 // the host.  Host code only; it needs point/packed_walk.h, which libshray_instance.so's own units do not see.
 #pragma once
 

@@ -388,4 +388,14 @@ int shrayi_instance_set_forward_maps(shray_instance_set *set, void *hip_stream, 
     return SHRAY_OK;
 }
 
+int shrayi_instance_set_member_scene(const shray_instance_set *set, int32_t instance, shray_scene **scene)
+{
+    if (!set || !scene)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "set or scene is NULL");
+    if (instance < 0 || (size_t)instance >= set->scenes.size())
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "instance %d is not among the set's %zu", instance, set->scenes.size());
+    *scene = set->scenes[(size_t)instance];
+    return SHRAY_OK;
+}
+
 }   // extern "C"

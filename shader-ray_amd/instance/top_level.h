@@ -1,5 +1,5 @@
-// top_level.h -- the walk of an instance set's top level and what its five callers share (instance.hip: closest and any hit;
-// instance_multihit/: all hits; instance_point/: closest points; instance_near/: within-radius; instance_overlap/: boxes).  walk_top_level
+// top_level.h -- the walk of an instance set's top level and what its six callers share (instance.hip: closest and any hit;
+// instance_multihit/: all hits; instance_point/, instance_near/, instance_overlap/, instance_intersect/: points, boxes, triangles).  walk_top_level
 // is the only loop over TopNodes in device code; DESIGN.md sections 10, 16 and 20 argue it.  Beside it: the node and record
 // layout, a lane's widened slab test, the object ray (include/shader_ray_instance.h), a leaf's SceneView, and the accessors
 // through which another library reads a set's device arrays and forward maps.  Internal to the libraries; no kernel here.
@@ -144,3 +144,8 @@ extern "C" int shrayi_instance_set_device_arrays(const shray_instance_set *set, 
 // After a host update (and on first use) the upload is staged on that stream; after a device update the copy is the one
 // that update's commit wrote, in stream order.  Host-only; makes the set's device current and waits for nothing.
 extern "C" int shrayi_instance_set_forward_maps(shray_instance_set *set, void *hip_stream, const float **d_maps);
+
+// Not in the header: for libshray_instance_intersect.so, whose instance form checks a range of triangles against its
+// instance's scene before any launch.  The member scene of instance `instance`, as the set was created.  Host-only; reads
+// nothing back, waits for nothing and touches no device.
+extern "C" int shrayi_instance_set_member_scene(const shray_instance_set *set, int32_t instance, shray_scene **scene);

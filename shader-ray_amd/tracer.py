@@ -814,6 +814,19 @@ def intersect_params(max_triangles: int = 8, any_only: bool = False, skip_shared
     return op
 
 
+def _set_intersect_params(max_triangles: int = 8, any_only: bool = False, skip_shared: bool = False,
+                          skip_own: bool = False) -> N.IntersectParams:
+    """shray_intersect_params for the instanced query, filled here: libshray_instance_intersect.so does not need
+    libshray_intersect.so.  skip_own sets SHRAY_INTERSECT_SKIP_OWN_INSTANCE, which only the instance form accepts."""
+    op = N.IntersectParams()
+    op.struct_size = C.sizeof(N.IntersectParams)
+    op.max_triangles = max_triangles
+    op.flags = ((N.INTERSECT_ANY if any_only else 0) | (N.INTERSECT_SKIP_SHARED if skip_shared else 0) |
+                (N.INTERSECT_SKIP_OWN_INSTANCE if skip_own else 0))
+    op.reserved = 0
+    return op
+
+
 # a triangle buffer of the triangle-intersection query (include/shader_ray_intersect.h): 48 bytes per element
 TRIANGLE_DTYPE = np.dtype([("a", np.float32, 3), ("pad0", np.float32), ("b", np.float32, 3), ("pad1", np.float32), ("c", np.float32, 3),
                            ("pad2", np.float32)])
@@ -1347,6 +1360,112 @@ class InstanceSet:
         boxes = voxel_boxes(origin, cell, dims, device)
         nx, ny, nz = (int(d) for d in dims)
         return self.boxes_touched(boxes).reshape(nx, ny, nz)
+
+    def intersecting_triangles(self, triangles, max_triangles: int = 8, counts: bool = True, counters: bool = False, any_only: bool = False,
+                               skip_shared: bool = False):
+        """Instanced triangle-intersection queries (include/shader_ray_instance_intersect.h): per world query triangle the
+        number of (instance, triangle) pairs it intersects, tested on the instances' triangles mapped to the world by the
+        set's object-to-world floats, and the `max_triangles` smallest of them in (instance, triangle) order, the other slots
+        SHRAY_HIT_MISS (-1) with instance -1.  `triangles` as for Scene.intersecting_triangles: host triangles take the
+        blocking path and return (indices: int32 [n, max_triangles], instances: int32 [n, max_triangles], counts: int32 [n]);
+        a float32 [n, 9] / [n, 12] GPU tensor on the set's device takes the device path on the current torch stream and
+        returns tensors of the same shapes.  counts=False returns None for the counts and lets a query that holds
+        `max_triangles` pairs skip the instances above them (the same indices); max_triangles = 0 returns None for the indices
+        and instances.  any_only=True (with max_triangles = 0) sets SHRAY_INTERSECT_ANY: the count is 1 or 0 and a query stops
+        at its first member.  skip_shared=True sets SHRAY_INTERSECT_SKIP_SHARED, judged on world corners.  counters=True (host
+        triangles only) also returns the counters of the walk that does not prune, summed over a query's walks."""
+        lib = N.load_instance_intersect()
+        return _first_k(self._handle, (lib.shray_intersect_triangles_instances_device, lib.shray_intersect_triangles_instances,
+                                       lib.shray_intersect_triangles_instances_counters),
+                        _set_intersect_params(max_triangles, any_only, skip_shared), max_triangles, "max_triangles", triangles, "triangles",
+                        self._device_triangles, _host_triangles, np.int32, (), True, counts, counters)
+
+    def _device_triangles(self, triangles):
+        """a GPU triangle tensor on the set's device as a contiguous shray_triangle tensor (Scene._device_triangles's forms)"""
+        if triangles.device.index != self.device:
+            raise ValueError(f"triangles are on {triangles.device}, the set on cuda:{self.device}")
+        return self._scenes[0]._device_triangles(triangles)
+
+    def intersecting_triangles_into(self, triangles_ptr: int, count: int, out_ptr: int, instances_ptr: int = 0, counts_ptr: int = 0,
+                                    max_triangles: int = 8, any_only: bool = False, skip_shared: bool = False, stream_ptr: int = 0):
+        """Asynchronous instanced triangle-intersection queries on device memory of the set's device
+        (shray_intersect_triangles_instances_device): `count` shray_triangle records at `triangles_ptr` -> count *
+        max_triangles int32 triangle indices at `out_ptr` (0 iff max_triangles is 0), unless `instances_ptr` is 0 count *
+        max_triangles int32 instance indices there, and unless `counts_ptr` is 0 `count` int32 counts there, on a HIP stream
+        (`stream_ptr`)."""
+        op = _set_intersect_params(max_triangles, any_only, skip_shared)
+        N.check(N.load_instance_intersect().shray_intersect_triangles_instances_device(
+            self._handle, C.byref(op), C.c_void_p(triangles_ptr), count, C.c_void_p(out_ptr or None), C.c_void_p(instances_ptr or None),
+            C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+
+    def intersection_counts(self, triangles, skip_shared: bool = False):
+        """How many (instance, triangle) pairs each world query triangle intersects (intersecting_triangles with max_triangles
+        = 0): int32 [n], numpy for host triangles, a tensor for GPU triangles."""
+        return self.intersecting_triangles(triangles, max_triangles=0, counts=True, skip_shared=skip_shared)[2]
+
+    def triangles_intersected(self, triangles, skip_shared: bool = False):
+        """Whether each world query triangle intersects any triangle of any instance (SHRAY_INTERSECT_ANY: a query stops at its
+        first member): bool [n], numpy for host triangles, a tensor for GPU triangles."""
+        return self.intersecting_triangles(triangles, max_triangles=0, counts=True, any_only=True, skip_shared=skip_shared)[2] != 0
+
+    def triangle_count(self, instance: int) -> int:
+        """The number of triangles of instance `instance`'s scene."""
+        if not 0 <= instance < self.count:
+            raise ValueError(f"instance {instance} is not among the set's {self.count}")
+        return self._scenes[instance].triangle_count()
+
+    def instance_intersections(self, instance: int, max_triangles: int = 8, counts: bool = True, any_only: bool = False,
+                               skip_shared: bool = False, skip_own: bool = True, first: int = 0, count: int | None = None,
+                               device: bool = False):
+        """The instance form (shray_intersect_instance): the queries are the triangles [first, first + count) of instance
+        `instance`'s scene (count=None: up to the last one) under that instance's current map, read on the device when the
+        query runs.  Returns (indices: int32 [count, max_triangles], instances: int32 [count, max_triangles], counts: int32
+        [count]) as numpy arrays from the blocking form, or with device=True as tensors on the set's device enqueued on the
+        current torch stream (shray_intersect_instance_device).  skip_own defaults to True here
+        (SHRAY_INTERSECT_SKIP_OWN_INSTANCE): no pair of instance `instance` itself is a member -- by its index, so a duplicate
+        instance at the same place is found.  max_triangles = 0 returns None for the indices and instances, counts=False None
+        for the counts; any_only and skip_shared as for intersecting_triangles."""
+        if max_triangles == 0 and not counts:
+            raise ValueError("nothing is asked for: max_triangles is 0 and counts is False")
+        triangles = self.triangle_count(instance) if 0 <= instance < self.count else 0   # (the library refuses another instance)
+        if count is None:
+            count = max(triangles - first, 0)
+        op = _set_intersect_params(max_triangles, any_only, skip_shared, skip_own)
+        lib = N.load_instance_intersect()
+        rows = count if first >= 0 and 0 <= count <= triangles - first else 0   # (the library refuses any other range)
+        if device:
+            import torch
+            where = torch.device("cuda", self.device)
+            # (an empty tensor has no pointer: one row is allocated for an empty range)
+            new = lambda want, *shape: torch.empty((max(rows, 1), *shape), dtype=torch.int32, device=where) if want else None
+            outs = (new(max_triangles > 0, max_triangles), new(max_triangles > 0, max_triangles), new(counts))
+            N.check(lib.shray_intersect_instance_device(self._handle, C.byref(op), instance, first, count,
+                                                        *(C.c_void_p(o.data_ptr() if o is not None else None) for o in outs),
+                                                        C.c_void_p(torch.cuda.current_stream(where).cuda_stream)))
+            return tuple(None if o is None else o[:rows] for o in outs)
+        new = lambda want, *shape: np.empty((rows, *shape), np.int32) if want else None
+        out, inst, n = new(max_triangles > 0, max_triangles), new(max_triangles > 0, max_triangles), new(counts)
+        N.check(lib.shray_intersect_instance(self._handle, C.byref(op), instance, first, count,
+                                             *(o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (out, inst, n))))
+        return out, inst, n
+
+    def instance_intersections_into(self, instance: int, first: int, count: int, out_ptr: int, instances_ptr: int = 0,
+                                    counts_ptr: int = 0, max_triangles: int = 8, any_only: bool = False, skip_shared: bool = False,
+                                    skip_own: bool = True, stream_ptr: int = 0):
+        """Asynchronous instance form (shray_intersect_instance_device): the triangles [first, first + count) of instance
+        `instance` -> count * max_triangles int32 triangle indices at `out_ptr` (0 iff max_triangles is 0), unless
+        `instances_ptr` is 0 as many instance indices there, and unless `counts_ptr` is 0 `count` int32 counts there, device
+        memory of the set's device, on a HIP stream (`stream_ptr`)."""
+        op = _set_intersect_params(max_triangles, any_only, skip_shared, skip_own)
+        N.check(N.load_instance_intersect().shray_intersect_instance_device(
+            self._handle, C.byref(op), instance, first, count, C.c_void_p(out_ptr or None), C.c_void_p(instances_ptr or None),
+            C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+
+    def instances_colliding(self) -> np.ndarray:
+        """bool [n]: instance i has a triangle that intersects a triangle of another instance (one SHRAY_INTERSECT_ANY |
+        SHRAY_INTERSECT_SKIP_OWN_INSTANCE launch of the instance form per instance)."""
+        return np.array([bool(self.instance_intersections(i, max_triangles=0, counts=True, any_only=True)[2].any())
+                         for i in range(self.count)], bool)
 
     def close(self):
         if getattr(self, "_handle", None):
