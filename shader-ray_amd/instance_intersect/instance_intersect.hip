@@ -4,7 +4,7 @@
 //
 // One lane per query in one-wave workgroups.  The wave walks the set's top level uniformly (instance/top_level.h's
 // walk_top_level): a lane enters a node unless an axis separates the node's stored box from its query's vertex box, and near
-// zero an axis may not separate (kGuard below, instance_overlap/instance_overlap.hip's).  At a leaf the instance is
+// zero an axis may not separate (instance/image_box.h's kGuard).  At a leaf the instance is
 // wave-uniform: its forward map's three rows and the member's SceneView come in by scalar loads, and the entering lanes run the
 // walk of intersect/intersect.hip over that member's packed tree with every box replaced by its image box under the map and
 // every triangle's corners mapped before the per-pair test.  A lane's K smallest carry from one instance into the next under
@@ -16,10 +16,10 @@
 //
 // The K smallest are kept as instance_overlap.hip keeps them: in registers for K <= 8 (one 64-bit key a slot, every index a
 // compile-time constant, no scratch), else the triangles in the query's own K output slots and the instances in the instance
-// buffer beside them.  image_box, the corner mapping, the guard and Held restate instance_overlap.hip's, min3 ..
-// triangle_intersects restate intersect.hip's: moving them to a header would put those libraries' units on another include
-// path.  This library is built apart from libshray_hip.so, libshray_instance.so, libshray_intersect.so,
-// libshray_instance_overlap.so and libshray_instance_point.so, so their code objects do not change.
+// buffer beside them (instance/held_pairs.h's Held).  The image boxes, the corner mapping and the guard are
+// instance/image_box.h's, the per-pair test point/triangle_pair_test.h's: this library compiles the code that
+// libshray_instance_overlap.so and libshray_intersect.so compile.  It is built apart from libshray_hip.so and
+// libshray_instance.so, so their code objects do not change.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -27,19 +27,18 @@
 #include "client_internal.h"
 #include "enter_set.h"
 #include "first_k_query.h"
+#include "held_pairs.h"
+#include "image_box.h"
 #include "packed_walk.h"
+#include "params_check.h"
 #include "shader_ray_instance_intersect.h"
 #include "top_level.h"
 #include "trace_common.h"
+#include "triangle_pair_test.h"
 
 using namespace shray;
 
 namespace {
-
-constexpr unsigned long long kEmptyKey = ~0ull;   // after every (instance, triangle)
-
-// Below this magnitude a stored top-level float and the query float beside it may not separate an axis.
-constexpr float kGuard = 0x1p-109f;
 
 struct SetIntersectWork {
     const float4 *triangles;   // three per query: (a, pad), (b, pad), (c, pad), world space; nullptr: the instance form
@@ -55,210 +54,6 @@ struct SetIntersectWork {
     uint32_t skip_shared;      // SHRAY_INTERSECT_SKIP_SHARED is set
     uint32_t skip_own;         // SHRAY_INTERSECT_SKIP_OWN_INSTANCE is set
     DeviceCounters *counters;
-};
-
-// include/shader_ray_intersect.h's min and max: comparisons, so that a NaN is passed on or dropped as the header's are
-__device__ __forceinline__ float min2(float x, float y) { return x < y ? x : y; }
-__device__ __forceinline__ float max2(float x, float y) { return x > y ? x : y; }
-__device__ __forceinline__ float min3(float x, float y, float z) { return min2(min2(x, y), z); }
-__device__ __forceinline__ float max3(float x, float y, float z) { return max2(max2(x, y), z); }
-
-__device__ __forceinline__ float dot(const float x[3], const float y[3]) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
-
-__device__ __forceinline__ void cross(float out[3], const float x[3], const float y[3])
-{
-    out[0] = x[1] * y[2] - x[2] * y[1];
-    out[1] = x[2] * y[0] - x[0] * y[2];
-    out[2] = x[0] * y[1] - x[1] * y[0];
-}
-
-__device__ __forceinline__ bool all_zero(const float x[3]) { return x[0] == 0.0f && x[1] == 0.0f && x[2] == 0.0f; }
-
-__device__ __forceinline__ bool same_corner(const float x[3], const float y[3]) { return x[0] == y[0] && x[1] == y[1] && x[2] == y[2]; }
-
-// What a lane keeps of its query, as intersect.hip does: the world corners (stage 0's box is lo, hi; the shared-corner stage
-// compares p), the translated corners q1 and q2 (q0 is exactly 0 for the finite queries that are walked) and the normal.  The
-// edges and the in-plane axes nq x f are recomputed per pair, after the stages that reject most.
-struct Query {
-    float p[3][3];
-    float lo[3], hi[3];
-    float q1[3], q2[3];
-    float nq[3];
-};
-
-// the query's interval on axis A: q0 = 0 is projected like the others (an infinite A gives the header's NaN)
-__device__ __forceinline__ bool axis_separates(const float A[3], const float v0[3], const float v1[3], const float v2[3], const Query &q)
-{
-    const float zero[3] = {0.0f, 0.0f, 0.0f};
-    const float s0 = dot(A, v0), s1 = dot(A, v1), s2 = dot(A, v2);
-    const float t0 = dot(A, zero), t1 = dot(A, q.q1), t2 = dot(A, q.q2);
-    return min3(s0, s1, s2) > max3(t0, t1, t2) || max3(s0, s1, s2) < min3(t0, t1, t2);
-}
-
-// include/shader_ray_intersect.h's per-pair test of the world triangle at `tri` (nine floats)
-__device__ __forceinline__ bool triangle_intersects(const Query &q, bool skip_shared, const float *tri)
-{
-    float a[3], b[3], c[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-        a[j] = tri[j], b[j] = tri[3 + j], c[j] = tri[6 + j];
-    // stage 0: the two vertex boxes, on the untranslated coordinates
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-        if (min3(a[j], b[j], c[j]) > q.hi[j] || max3(a[j], b[j], c[j]) < q.lo[j])
-            return false;
-    if (skip_shared) {
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-            if (same_corner(a, q.p[i]) || same_corner(b, q.p[i]) || same_corner(c, q.p[i]))
-                return false;
-    }
-    const float zero[3] = {0.0f, 0.0f, 0.0f};
-    float v[3][3], e[3][3], f[3][3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        v[0][j] = a[j] - q.p[0][j], v[1][j] = b[j] - q.p[0][j], v[2][j] = c[j] - q.p[0][j];
-        e[0][j] = v[1][j] - v[0][j], e[1][j] = v[2][j] - v[1][j], e[2][j] = v[0][j] - v[2][j];
-        f[0][j] = q.q1[j] - zero[j], f[1][j] = q.q2[j] - q.q1[j], f[2][j] = zero[j] - q.q2[j];
-    }
-    float nt[3];
-    cross(nt, e[0], e[1]);
-    if (all_zero(nt))
-        return false;
-    if (axis_separates(q.nq, v[0], v[1], v[2], q) || axis_separates(nt, v[0], v[1], v[2], q))
-        return false;
-    float A[3];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            cross(A, f[i], e[j]);
-            if (axis_separates(A, v[0], v[1], v[2], q))
-                return false;
-        }
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        cross(A, q.nq, f[i]);
-        if (axis_separates(A, v[0], v[1], v[2], q))
-            return false;
-    }
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        cross(A, nt, e[j]);
-        if (axis_separates(A, v[0], v[1], v[2], q))
-            return false;
-    }
-    return true;
-}
-
-// the image of a node's box under the map's rows: per world axis the corner formula on the ends that make it smallest and
-// largest, chosen by the signs of the row's entries alone (a zero entry is not read: either end)
-__device__ __forceinline__ Box image_box(const float4 (&m)[3], const Box &b)
-{
-    Box o;
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        const float row[3] = {m[r].x, m[r].y, m[r].z};
-        float lo[3], hi[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            lo[c] = row[c] < 0.0f ? b.hi[c] : b.lo[c];
-            hi[c] = row[c] < 0.0f ? b.lo[c] : b.hi[c];
-        }
-        o.lo[r] = object_row(m[r], mk(lo[0], lo[1], lo[2]), true);
-        o.hi[r] = object_row(m[r], mk(hi[0], hi[1], hi[2]), true);
-    }
-    return o;
-}
-
-// a member node's cull: its image box against the query's vertex box, six comparisons; a NaN end compares false and culls less
-__device__ __forceinline__ bool image_overlaps(const float4 (&m)[3], const Box &node, const float lo[3], const float hi[3])
-{
-    const Box o = image_box(m, node);
-    return !(o.hi[0] < lo[0] || o.lo[0] > hi[0] || o.hi[1] < lo[1] || o.lo[1] > hi[1] || o.hi[2] < lo[2] || o.lo[2] > hi[2]);
-}
-
-// one comparison of a top-level node's cull: the stored end lies beyond the query end, and the two are not both near zero
-__device__ __forceinline__ bool guarded(bool beyond, float stored, float query)
-{
-    return beyond && !(fabsf(stored) < kGuard && fabsf(query) < kGuard);
-}
-
-// a top-level node's cull: its stored box (a, b) against the query's vertex box
-__device__ __forceinline__ bool stored_overlaps(const float4 &a, const float4 &b, const float lo[3], const float hi[3])
-{
-    return !(guarded(b.x < lo[0], b.x, lo[0]) || guarded(a.x > hi[0], a.x, hi[0]) || guarded(b.y < lo[1], b.y, lo[1]) ||
-             guarded(a.y > hi[1], a.y, hi[1]) || guarded(b.z < lo[2], b.z, lo[2]) || guarded(a.z > hi[2], a.z, hi[2]));
-}
-
-// triangle t of `positions` under the map m: nine world floats (include/shader_ray_instance_point.h's formula)
-__device__ __forceinline__ void mapped_corners(const float4 (&m)[3], const float *positions, uint64_t t, float c9[9])
-{
-    const float *v = positions + 9ull * t;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const V3 corner = mk(v[3 * k], v[3 * k + 1], v[3 * k + 2]);
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-            c9[3 * k + r] = object_row(m[r], corner, true);
-    }
-}
-
-__device__ __forceinline__ unsigned long long key_of(int inst, uint32_t tri) { return ((unsigned long long)(uint32_t)inst << 32) | tri; }
-
-// A lane's K smallest.  SLOTS > 0: the keys in registers, ascending; kSlotsInMemory: the triangles in the query's own output
-// slots and their instances beside them (any k, also 0).
-template <int SLOTS>
-struct Held {
-    static constexpr int R = SLOTS > 0 ? SLOTS : 1;
-    unsigned long long key[R];   // (plain scalars: every index is a constant once unrolled)
-    int32_t *slots;              // in memory: this query's own triangles and instances (dereferenced only when live and k > 0)
-    int32_t *slot_inst;
-    int k;
-
-    // the pair sinks to where it sorts, the largest falls off
-    __device__ __forceinline__ void insert(int inst, uint32_t t)
-    {
-        if (SLOTS != kSlotsInMemory) {
-            unsigned long long carry = key_of(inst, t);
-#pragma unroll
-            for (int i = 0; i < R; i++) {
-                const unsigned long long low = carry < key[i] ? carry : key[i];
-                carry = carry < key[i] ? key[i] : carry;
-                key[i] = low;
-            }
-        } else if (k > 0 && before(inst, t, slot_inst[k - 1], slots[k - 1])) {
-            int i = k - 1;
-            while (i > 0) {
-                const int32_t st = slots[i - 1], si = slot_inst[i - 1];
-                if (!before(inst, t, si, st))
-                    break;
-                slots[i] = st, slot_inst[i] = si;
-                i--;
-            }
-            slots[i] = (int32_t)t, slot_inst[i] = inst;
-        }
-    }
-
-    // the key of the header against a slot in memory; an empty slot (triangle < 0) is after every pair
-    static __device__ __forceinline__ bool before(int inst, uint32_t t, int32_t slot_inst, int32_t slot_tri)
-    {
-        return slot_tri < 0 || inst < slot_inst || (inst == slot_inst && t < (uint32_t)slot_tri);
-    }
-
-    // whether K pairs are held and every one of them is of an instance below `inst`: no pair of `inst` can be among the K
-    // smallest, because the key leads with the instance
-    __device__ __forceinline__ bool full_below(int inst) const
-    {
-        if (SLOTS != kSlotsInMemory) {
-            unsigned long long last = kEmptyKey;
-#pragma unroll
-            for (int i = 0; i < R; i++)
-                last = i == k - 1 ? key[i] : last;
-            return last != kEmptyKey && (uint32_t)inst > (uint32_t)(last >> 32);
-        }
-        return k > 0 && slots[k - 1] >= 0 && inst > slot_inst[k - 1];
-    }
 };
 
 // One lane's walk of instance `inst`: intersect.hip's loop over the member's packed tree, on image boxes and mapped corners.
@@ -435,7 +230,7 @@ __global__ void __launch_bounds__(kBlock) instance_intersect_kernel(SetIntersect
 }
 
 constexpr Nouns kNouns = {"triangle", "triangles", "set", "out", "max_triangles", "instanced triangle-intersection query"};
-constexpr uint32_t kItemFlags = SHRAY_INTERSECT_ANY | SHRAY_INTERSECT_SKIP_SHARED;
+constexpr uint32_t kItemFlags = SHRAY_INTERSECT_ANY | SHRAY_INTERSECT_SKIP_SHARED;   // only the instance form knows SKIP_OWN_INSTANCE
 
 // where a form's queries come from: the item array, or the triangles [first, first + count) of instance `instance`
 struct Source {
@@ -444,30 +239,12 @@ struct Source {
     int64_t first;
 };
 
-// include/shader_ray_intersect.h's params check with the misuse of SHRAY_INTERSECT_ANY; only the instance form knows
-// SHRAY_INTERSECT_SKIP_OWN_INSTANCE
-int check_params(const shray_intersect_params *op, const void *counts, bool own)
-{
-    if (!op)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "intersect params are NULL");
-    if (op->struct_size != sizeof(shray_intersect_params))
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "shray_intersect_params.struct_size is %u, this library expects %zu", op->struct_size,
-                    sizeof(shray_intersect_params));
-    const uint32_t known = kItemFlags | (own ? (uint32_t)SHRAY_INTERSECT_SKIP_OWN_INSTANCE : 0u);
-    if (op->max_triangles < 0 || op->max_triangles > SHRAY_INTERSECT_MAX || (op->flags & ~known) || op->reserved != 0)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "intersect params out of range (max_triangles %d of 0 .. %d, flags 0x%x, reserved %d)",
-                    op->max_triangles, (int)SHRAY_INTERSECT_MAX, op->flags, op->reserved);
-    if ((op->flags & SHRAY_INTERSECT_ANY) && (op->max_triangles != 0 || !counts))
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "SHRAY_INTERSECT_ANY needs max_triangles 0 (it is %d) and counts", op->max_triangles);
-    return SHRAY_OK;
-}
-
 // The checks every form makes before it touches a device.  The instance form's `triangles` is its set (it has no item array).
 int check_query(shray_instance_set *set, const shray_intersect_params *op, const Source &src, const void *triangles, int64_t count,
                 const void *out, const void *instances, const void *counts)
 {
-    int rc = check_params(op, counts, src.own);
-    if (rc)
+    int rc = check_params(op, kItemFlags | (src.own ? (uint32_t)SHRAY_INTERSECT_SKIP_OWN_INSTANCE : 0u));
+    if (rc || (rc = check_any(op, counts)))
         return rc;
     if (src.own) {
         if (src.first < 0)
@@ -512,60 +289,38 @@ int intersect_device(shray_instance_set *set, const shray_intersect_params *op, 
     const bool any = (op->flags & SHRAY_INTERSECT_ANY) != 0;
     if (count == 0)
         return SHRAY_OK;
-    ShrayInstanceSetDevice d;
-    int height = 0;
-    if ((rc = enter_set(set, &d, &height)))
-        return rc;
-    const float *d_maps = nullptr;
-    if ((rc = shrayi_instance_set_forward_maps(set, stream, &d_maps)))
-        return rc;
-    // the form that keeps its K smallest in the query's output slots keeps the instance half of the keys beside them: without
-    // an instance buffer of the caller's, in scratch that is taken and given back in stream order
-    int32_t *scratch = nullptr;
-    if (kept_in_memory(k) && !d_instances) {
-        HIP_TRY(hipMallocAsync((void **)&scratch, (size_t)count * (size_t)k * sizeof(int32_t), stream));
-        d_instances = scratch;
-    }
-    const int levels = (int)stack_levels(height);
-    SetIntersectWork w{src.own ? nullptr : (const float4 *)d_triangles,
-                       k > 0 ? d_out : nullptr,
-                       k > 0 ? d_instances : nullptr,
-                       d_counts,
-                       (uint64_t)count,
-                       0,
-                       src.own ? (uint64_t)src.first : 0,
-                       src.own ? src.instance : -1,
-                       k,
-                       levels,
-                       (op->flags & SHRAY_INTERSECT_SKIP_SHARED) ? 1u : 0u,
-                       (op->flags & SHRAY_INTERSECT_SKIP_OWN_INSTANCE) ? 1u : 0u,
-                       d_counters};
-    const size_t lds = (size_t)kBlock * (size_t)levels * sizeof(uint32_t) + kTopStack * sizeof(uint32_t);
-    const TopNode *nodes = static_cast<const TopNode *>(d.nodes);
-    const float4 *records = static_cast<const float4 *>(d.records);
-    const float4 *maps = reinterpret_cast<const float4 *>(d_maps);
-    const SceneView *views = static_cast<const SceneView *>(d.views);
-    rc = first_k_launches(kNouns, w, count, [&](dim3 grid) {
-        if (any && d_counters)
-            hipLaunchKernelGGL((instance_intersect_kernel<kSlotsInMemory, false, true, true>), grid, dim3(kBlock), lds, stream, w, nodes,
-                               records, maps, views);
-        else if (any)
-            hipLaunchKernelGGL((instance_intersect_kernel<kSlotsInMemory, false, false, true>), grid, dim3(kBlock), lds, stream, w, nodes,
-                               records, maps, views);
-        else
-            with_slots(k, [&](auto slots) {
-                with_form(form_for(d_counters, d_counts, k), [&](auto prune, auto tally) {
-                    hipLaunchKernelGGL((instance_intersect_kernel<decltype(slots)::value, decltype(prune)::value, decltype(tally)::value, false>),
-                                       grid, dim3(kBlock), lds, stream, w, nodes, records, maps, views);
+    return walk_set(set, true, k, count, d_instances, stream, [&](const SetWalk &s) {
+        SetIntersectWork w{src.own ? nullptr : (const float4 *)d_triangles,
+                           k > 0 ? d_out : nullptr,
+                           k > 0 ? s.instances : nullptr,
+                           d_counts,
+                           (uint64_t)count,
+                           0,
+                           src.own ? (uint64_t)src.first : 0,
+                           src.own ? src.instance : -1,
+                           k,
+                           s.levels,
+                           (op->flags & SHRAY_INTERSECT_SKIP_SHARED) ? 1u : 0u,
+                           (op->flags & SHRAY_INTERSECT_SKIP_OWN_INSTANCE) ? 1u : 0u,
+                           d_counters};
+        const size_t lds = s.lds(sizeof(uint32_t));
+        return first_k_launches(kNouns, w, count, [&](dim3 grid) {
+            if (any && d_counters)
+                hipLaunchKernelGGL((instance_intersect_kernel<kSlotsInMemory, false, true, true>), grid, dim3(kBlock), lds, stream, w, s.nodes,
+                                   s.records, s.maps, s.views);
+            else if (any)
+                hipLaunchKernelGGL((instance_intersect_kernel<kSlotsInMemory, false, false, true>), grid, dim3(kBlock), lds, stream, w, s.nodes,
+                                   s.records, s.maps, s.views);
+            else
+                with_slots(k, [&](auto slots) {
+                    with_form(form_for(d_counters, d_counts, k), [&](auto prune, auto tally) {
+                        hipLaunchKernelGGL(
+                            (instance_intersect_kernel<decltype(slots)::value, decltype(prune)::value, decltype(tally)::value, false>), grid,
+                            dim3(kBlock), lds, stream, w, s.nodes, s.records, s.maps, s.views);
+                    });
                 });
-            });
+        });
     });
-    if (scratch) {
-        const hipError_t e = hipFreeAsync(scratch, stream);
-        if (e != hipSuccess && !rc)
-            rc = fail(SHRAY_ERR_DEVICE, "hipFreeAsync failed: %s", hipGetErrorString(e));
-    }
-    return rc;
 }
 
 // the blocking forms: the triangles to the device (none for the instance form), the query on the null stream, the indices,
@@ -580,11 +335,7 @@ int intersect_host(shray_instance_set *set, const shray_intersect_params *op, co
     return first_k_blocking(
         {src.own ? (const void *)no_items : triangles, src.own ? 0 : sizeof(shray_triangle), out, sizeof(int32_t), instances, counts}, count,
         op->max_triangles, tallies,
-        [&] {
-            ShrayInstanceSetDevice d;
-            int height = 0;
-            return enter_set(set, &d, &height);
-        },
+        [&] { return enter_set(set); },
         [&](void *d_triangles, void *d_out, int32_t *d_instances, int32_t *d_counts, DeviceCounters *shards) {
             return intersect_device(set, op, src, (const shray_triangle *)d_triangles, count, (int32_t *)d_out, d_instances, d_counts, nullptr,
                                     shards);

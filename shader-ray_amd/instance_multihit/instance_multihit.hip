@@ -105,38 +105,20 @@ int trace_device(shray_instance_set *set, const shray_multihit_params *mp, const
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "ray and hit buffers must be 16-byte aligned, the instances and counts 4-byte aligned");
     if (count == 0)
         return SHRAY_OK;
-    ShrayInstanceSetDevice d;
-    int height = 0;
-    if ((rc = enter_set(set, &d, &height)))
-        return rc;
-    // the form that keeps its K best in the ray's output slots keeps the instance half of the keys there too: without an
-    // instance buffer of the caller's, in scratch that is taken and given back in stream order
-    int32_t *scratch = nullptr;
-    if (kept_in_memory(k) && !d_instances) {
-        HIP_TRY(hipMallocAsync((void **)&scratch, (size_t)count * (size_t)k * sizeof(int32_t), stream));
-        d_instances = scratch;
-    }
-    const int levels = (int)stack_levels(height);
-    SetWork w{(const float4 *)d_rays, k > 0 ? (float4 *)d_hits : nullptr, k > 0 ? d_instances : nullptr, d_counts, (uint64_t)count, 0, k,
-              mp->max_leaf_tests, levels, d_counters};
-    const size_t lds = ((size_t)kBlock * (size_t)levels + kTopStack) * sizeof(uint32_t);
-    const TopNode *nodes = static_cast<const TopNode *>(d.nodes);
-    const float4 *records = static_cast<const float4 *>(d.records);
-    const SceneView *views = static_cast<const SceneView *>(d.views);
-    rc = first_k_launches(kNouns, w, count, [&](dim3 grid) {
-        with_slots(k, [&](auto slots) {
-            with_form(form_for(d_counters, d_counts, k), [&](auto prune, auto tally) {
-                hipLaunchKernelGGL((instance_all_hits_kernel<decltype(slots)::value, decltype(prune)::value, decltype(tally)::value>), grid,
-                                   dim3(kBlock), lds, stream, w, nodes, records, views);
+    // (rays go into an instance's object space: the forward maps are not asked for)
+    return walk_set(set, false, k, count, d_instances, stream, [&](const SetWalk &s) {
+        SetWork w{(const float4 *)d_rays, k > 0 ? (float4 *)d_hits : nullptr, k > 0 ? s.instances : nullptr, d_counts, (uint64_t)count, 0, k,
+                  mp->max_leaf_tests, s.levels, d_counters};
+        const size_t lds = s.lds(sizeof(uint32_t));
+        return first_k_launches(kNouns, w, count, [&](dim3 grid) {
+            with_slots(k, [&](auto slots) {
+                with_form(form_for(d_counters, d_counts, k), [&](auto prune, auto tally) {
+                    hipLaunchKernelGGL((instance_all_hits_kernel<decltype(slots)::value, decltype(prune)::value, decltype(tally)::value>), grid,
+                                       dim3(kBlock), lds, stream, w, s.nodes, s.records, s.views);
+                });
             });
         });
     });
-    if (scratch) {
-        const hipError_t e = hipFreeAsync(scratch, stream);
-        if (e != hipSuccess && !rc)
-            rc = fail(SHRAY_ERR_DEVICE, "hipFreeAsync failed: %s", hipGetErrorString(e));
-    }
-    return rc;
 }
 
 // the blocking forms: the rays to the device, the query on the null stream, the records, instances, counts (and tallies) back
@@ -147,11 +129,7 @@ int trace_host(shray_instance_set *set, const shray_multihit_params *mp, const s
         return rc;
     return first_k_blocking(
         {rays, sizeof(shray_ray), hits, sizeof(shray_hit), instances, counts}, count, mp->max_hits, out,
-        [&] {
-            ShrayInstanceSetDevice d;
-            int height = 0;
-            return enter_set(set, &d, &height);
-        },
+        [&] { return enter_set(set); },
         [&](void *d_rays, void *d_hits, int32_t *d_instances, int32_t *d_counts, DeviceCounters *shards) {
             return trace_device(set, mp, (const shray_ray *)d_rays, count, (shray_hit *)d_hits, d_instances, d_counts, nullptr, shards);
         });

@@ -14,10 +14,9 @@
 // compile-time constant, no scratch), the winners' records computed again at the end by the same function on the same mapped
 // corners (the winners' instances are not wave-uniform, so the map and the positions then come by per-lane loads); for
 // larger K the whole records are inserted into the point's own K output slots and the instances into the instance buffer.
-// image_box, image_bound and the corner mapping restate instance_point.hip's: moving them to a header would put
-// libshray_instance_point.so's unit on another include path.
-// This library is built apart from libshray_hip.so, libshray_instance.so, libshray_near.so and libshray_instance_point.so,
-// so their code objects do not change.
+// The image boxes, their bound and the corner mapping are instance/image_box.h's: this library compiles the code that
+// libshray_instance_point.so compiles.  It is built apart from libshray_hip.so and libshray_instance.so, so their code objects
+// do not change.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -26,6 +25,7 @@
 #include "closest_on_triangle.h"
 #include "enter_set.h"
 #include "first_k_query.h"
+#include "image_box.h"
 #include "packed_walk.h"
 #include "shader_ray_instance_near.h"
 #include "top_level.h"
@@ -67,45 +67,10 @@ __device__ __forceinline__ bool before(float d, int inst, int tri, float slot_d,
     return slot_tri < 0 || d < slot_d || (d == slot_d && (inst < slot_inst || (inst == slot_inst && tri < slot_tri)));
 }
 
-// the image of a node's box under the map's rows: per world axis the corner formula on the ends that make it smallest and
-// largest, chosen by the signs of the row's entries alone (a zero entry is not read: either end)
-__device__ __forceinline__ Box image_box(const float4 (&m)[3], const Box &b)
-{
-    Box o;
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        const float row[3] = {m[r].x, m[r].y, m[r].z};
-        float lo[3], hi[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            lo[c] = row[c] < 0.0f ? b.hi[c] : b.lo[c];
-            hi[c] = row[c] < 0.0f ? b.lo[c] : b.hi[c];
-        }
-        o.lo[r] = object_row(m[r], mk(lo[0], lo[1], lo[2]), true);
-        o.hi[r] = object_row(m[r], mk(hi[0], hi[1], hi[2]), true);
-    }
-    return o;
-}
-
-__device__ __forceinline__ float image_bound(const float4 (&m)[3], const float p[3], const Box &b)
-{
-    const Box o = image_box(m, b);
-    return box_bound(p, o.lo, o.hi);
-}
-
 // the record of the pair (the instance whose map is m, triangle t of its scene): the corners mapped, then the closest point
 __device__ __forceinline__ Closest closest_on_mapped(const float4 (&m)[3], const float *positions, uint32_t t, const float p[3])
 {
-    const float *v = positions + 9ull * t;
-    float c9[9];
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const V3 corner = mk(v[3 * k], v[3 * k + 1], v[3 * k + 2]);
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-            c9[3 * k + r] = object_row(m[r], corner, true);
-    }
-    return closest_on_triangle(p, c9);
+    return with_mapped_corners(m, positions, t, [&](const float *c9) { return closest_on_triangle(p, c9); });
 }
 
 // A lane's K best.  SLOTS > 0: the keys in registers; kSlotsInMemory: the records in the point's own output slots and
@@ -367,42 +332,19 @@ int near_device(shray_instance_set *set, const shray_near_params *np, const shra
                     "point and record buffers must be 16-byte aligned, the instances and counts 4-byte aligned");
     if (count == 0)
         return SHRAY_OK;
-    ShrayInstanceSetDevice d;
-    int height = 0;
-    if ((rc = enter_set(set, &d, &height)))
-        return rc;
-    const float *d_maps = nullptr;
-    if ((rc = shrayi_instance_set_forward_maps(set, stream, &d_maps)))
-        return rc;
-    // the form that keeps its K best in the point's output slots keeps the instance third of the keys beside them: without an
-    // instance buffer of the caller's, in scratch that is taken and given back in stream order
-    int32_t *scratch = nullptr;
-    if (kept_in_memory(k) && !d_instances) {
-        HIP_TRY(hipMallocAsync((void **)&scratch, (size_t)count * (size_t)k * sizeof(int32_t), stream));
-        d_instances = scratch;
-    }
-    const int levels = (int)stack_levels(height);
-    SetNearWork w{(const float4 *)d_points, k > 0 ? (float4 *)d_out : nullptr, k > 0 ? d_instances : nullptr, d_counts, (uint64_t)count, 0, k,
-                  levels, d_counters};
-    const size_t lds = (size_t)kBlock * (size_t)levels * sizeof(StackEntry) + kTopStack * sizeof(uint32_t);
-    const TopNode *nodes = static_cast<const TopNode *>(d.nodes);
-    const float4 *records = static_cast<const float4 *>(d.records);
-    const float4 *maps = reinterpret_cast<const float4 *>(d_maps);
-    const SceneView *views = static_cast<const SceneView *>(d.views);
-    rc = first_k_launches(kNouns, w, count, [&](dim3 grid) {
-        with_slots(k, [&](auto slots) {
-            with_form(form_for(d_counters, d_counts, k), [&](auto prune, auto tally) {
-                hipLaunchKernelGGL((instance_near_kernel<decltype(slots)::value, decltype(prune)::value, decltype(tally)::value>), grid,
-                                   dim3(kBlock), lds, stream, w, nodes, records, maps, views);
+    return walk_set(set, true, k, count, d_instances, stream, [&](const SetWalk &s) {
+        SetNearWork w{(const float4 *)d_points, k > 0 ? (float4 *)d_out : nullptr, k > 0 ? s.instances : nullptr, d_counts, (uint64_t)count, 0,
+                      k, s.levels, d_counters};
+        const size_t lds = s.lds(sizeof(StackEntry));
+        return first_k_launches(kNouns, w, count, [&](dim3 grid) {
+            with_slots(k, [&](auto slots) {
+                with_form(form_for(d_counters, d_counts, k), [&](auto prune, auto tally) {
+                    hipLaunchKernelGGL((instance_near_kernel<decltype(slots)::value, decltype(prune)::value, decltype(tally)::value>), grid,
+                                       dim3(kBlock), lds, stream, w, s.nodes, s.records, s.maps, s.views);
+                });
             });
         });
     });
-    if (scratch) {
-        const hipError_t e = hipFreeAsync(scratch, stream);
-        if (e != hipSuccess && !rc)
-            rc = fail(SHRAY_ERR_DEVICE, "hipFreeAsync failed: %s", hipGetErrorString(e));
-    }
-    return rc;
 }
 
 // the blocking forms: the points to the device, the query on the null stream, the records, instances, counts (and tallies) back
@@ -413,11 +355,7 @@ int near_host(shray_instance_set *set, const shray_near_params *np, const shray_
         return rc;
     return first_k_blocking(
         {points, sizeof(shray_point), out, sizeof(shray_closest), instances, counts}, count, np->max_near, tallies,
-        [&] {
-            ShrayInstanceSetDevice d;
-            int height = 0;
-            return enter_set(set, &d, &height);
-        },
+        [&] { return enter_set(set); },
         [&](void *d_points, void *d_out, int32_t *d_instances, int32_t *d_counts, DeviceCounters *shards) {
             return near_device(set, np, (const shray_point *)d_points, count, (shray_closest *)d_out, d_instances, d_counts, nullptr, shards);
         });

@@ -7,7 +7,9 @@
 // wave-uniform: its forward map's three rows and the member's SceneView come in by scalar loads, and the lanes whose bound
 // passes run the closest-point walk of that member's packed tree (point/point_walk.h's loop) with every box replaced by its
 // image box under the map and every triangle's corners mapped before closest_on_triangle.  A lane's best carries from one
-// instance into the next, with (instance, triangle) deciding a tie.
+// instance into the next, with (instance, triangle) deciding a tie.  The image boxes and their bound are
+// instance/image_box.h's, which the other instanced walks over a member's packed tree compile too; the corner mapping stays
+// spelled out in this walk, whose register allocation changes when it goes through that header's.
 // This library is built apart from libshray_hip.so, libshray_instance.so and libshray_point.so, so their code objects do not
 // change.
 #include <hip/hip_runtime.h>
@@ -17,6 +19,7 @@
 #include "client_internal.h"
 #include "closest_on_triangle.h"
 #include "enter_set.h"
+#include "image_box.h"
 #include "packed_walk.h"
 #include "shader_ray_instance_point.h"
 #include "top_level.h"
@@ -42,32 +45,6 @@ struct Best {
     int tri, inst;
     Closest found;
 };
-
-// the image of a node's box under the map's rows: per world axis the corner formula on the ends that make it smallest and
-// largest, chosen by the signs of the row's entries alone (a zero entry is not read: either end)
-__device__ __forceinline__ Box image_box(const float4 (&m)[3], const Box &b)
-{
-    Box o;
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        const float row[3] = {m[r].x, m[r].y, m[r].z};
-        float lo[3], hi[3];
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            lo[c] = row[c] < 0.0f ? b.hi[c] : b.lo[c];
-            hi[c] = row[c] < 0.0f ? b.lo[c] : b.hi[c];
-        }
-        o.lo[r] = object_row(m[r], mk(lo[0], lo[1], lo[2]), true);
-        o.hi[r] = object_row(m[r], mk(hi[0], hi[1], hi[2]), true);
-    }
-    return o;
-}
-
-__device__ __forceinline__ float image_bound(const float4 (&m)[3], const float p[3], const Box &b)
-{
-    const Box o = image_box(m, b);
-    return box_bound(p, o.lo, o.hi);
-}
 
 // One lane's walk of instance `inst`: point_walk.h's loop over the member's packed tree, on image boxes and mapped corners.
 __device__ __forceinline__ void instance_walk(const SceneView &sc, const float4 (&m)[3], int inst, const float p[3], uint2 *column,
@@ -218,29 +195,19 @@ int closest_device(shray_instance_set *set, const shray_point *d_points, int64_t
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "point and record buffers must be 16-byte aligned, the instance buffer 4-byte aligned");
     if (count == 0)
         return SHRAY_OK;
-    ShrayInstanceSetDevice d;
-    int height = 0;
-    int rc = enter_set(set, &d, &height);
-    if (rc)
-        return rc;
-    const float *d_maps = nullptr;
-    if ((rc = shrayi_instance_set_forward_maps(set, stream, &d_maps)))
-        return rc;
-    const int levels = height > 0 ? height : 1;
-    SetWork w{(const float4 *)d_points, (float4 *)d_out, d_instances, (uint64_t)count, 0, levels, d_counters};
-    const size_t lds = (size_t)kBlock * (size_t)levels * sizeof(uint2) + kTopStack * sizeof(uint32_t);
-    const TopNode *nodes = static_cast<const TopNode *>(d.nodes);
-    const float4 *records = static_cast<const float4 *>(d.records);
-    const float4 *maps = reinterpret_cast<const float4 *>(d_maps);
-    const SceneView *views = static_cast<const SceneView *>(d.views);
-    const uint64_t blocks = ((uint64_t)count + kBlock - 1) / kBlock;
-    return for_each_launch(blocks, kPointsPerLaunch / kBlock, [&](uint64_t first, dim3 grid) {
-        w.first = first * kBlock;
-        if (d_counters)
-            hipLaunchKernelGGL(instance_closest_kernel<true>, grid, dim3(kBlock), lds, stream, w, nodes, records, maps, views);
-        else
-            hipLaunchKernelGGL(instance_closest_kernel<false>, grid, dim3(kBlock), lds, stream, w, nodes, records, maps, views);
-        return launched("instanced closest-point");
+    // (one record per point, kept in registers: K is 0 to walk_set, which then takes no scratch)
+    return walk_set(set, true, 0, count, d_instances, stream, [&](const SetWalk &s) {
+        SetWork w{(const float4 *)d_points, (float4 *)d_out, s.instances, (uint64_t)count, 0, s.levels, d_counters};
+        const size_t lds = s.lds(sizeof(uint2));
+        const uint64_t blocks = ((uint64_t)count + kBlock - 1) / kBlock;
+        return for_each_launch(blocks, kPointsPerLaunch / kBlock, [&](uint64_t first, dim3 grid) {
+            w.first = first * kBlock;
+            if (d_counters)
+                hipLaunchKernelGGL(instance_closest_kernel<true>, grid, dim3(kBlock), lds, stream, w, s.nodes, s.records, s.maps, s.views);
+            else
+                hipLaunchKernelGGL(instance_closest_kernel<false>, grid, dim3(kBlock), lds, stream, w, s.nodes, s.records, s.maps, s.views);
+            return launched("instanced closest-point");
+        });
     });
 }
 
@@ -258,10 +225,7 @@ int closest_host(shray_instance_set *set, const shray_point *points, int64_t cou
     }
     if (count == 0)
         return SHRAY_OK;
-    ShrayInstanceSetDevice d;
-    int height = 0;
-    const int rc = enter_set(set, &d, &height);   // (the errors of a set come before any allocation)
-    if (rc)
+    if (const int rc = enter_set(set))   // (the errors of a set come before any allocation)
         return rc;
     const size_t n = (size_t)count;
     return run_blocking({{points, n * sizeof(shray_point)}}, {{out, n * sizeof(shray_closest)}, {instances, instances ? n * sizeof(int32_t) : 0}},

@@ -14,7 +14,8 @@
 // instances stay the twelve of overlap.hip (five slot counts and ANY, each with and without the work counters).
 //
 // The K smallest indices are kept by sorted insertion: in registers for K <= 8 (instances for 1, 2, 4 and 8 slots; every
-// index is a compile-time constant, so there is no scratch), else in the query's own K output slots.
+// index is a compile-time constant, so there is no scratch), else in the query's own K output slots.  The per-pair test is
+// point/triangle_pair_test.h's and the cull point/triangle_box_test.h's, which the instanced form compiles too.
 // This library is built apart from libshray_hip.so, so the renderer's and the other clients' code objects do not change.
 #include <hip/hip_runtime.h>
 
@@ -23,7 +24,9 @@
 #include "client_internal.h"
 #include "first_k_query.h"
 #include "packed_walk.h"
+#include "params_check.h"
 #include "shader_ray_intersect.h"
+#include "triangle_pair_test.h"
 
 using namespace shray;
 
@@ -42,107 +45,6 @@ struct IntersectWork {
     uint32_t skip_shared;      // SHRAY_INTERSECT_SKIP_SHARED is set
     DeviceCounters *counters;
 };
-
-// the header's min and max: comparisons, so that a NaN is passed on or dropped as the header's are
-__device__ __forceinline__ float min2(float x, float y) { return x < y ? x : y; }
-__device__ __forceinline__ float max2(float x, float y) { return x > y ? x : y; }
-__device__ __forceinline__ float min3(float x, float y, float z) { return min2(min2(x, y), z); }
-__device__ __forceinline__ float max3(float x, float y, float z) { return max2(max2(x, y), z); }
-
-__device__ __forceinline__ float dot(const float x[3], const float y[3]) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
-
-__device__ __forceinline__ void cross(float out[3], const float x[3], const float y[3])
-{
-    out[0] = x[1] * y[2] - x[2] * y[1];
-    out[1] = x[2] * y[0] - x[0] * y[2];
-    out[2] = x[0] * y[1] - x[1] * y[0];
-}
-
-__device__ __forceinline__ bool all_zero(const float x[3]) { return x[0] == 0.0f && x[1] == 0.0f && x[2] == 0.0f; }
-
-__device__ __forceinline__ bool same_corner(const float x[3], const float y[3]) { return x[0] == y[0] && x[1] == y[1] && x[2] == y[2]; }
-
-// What a lane keeps of its query: the corners (stage 0's box is lo, hi; the shared-corner stage compares p), the translated
-// corners q1 and q2 (q0 is exactly 0 for the finite queries that are walked) and the normal.  The edges (f0 = q1 - q0,
-// f1 = q2 - q1, f2 = q0 - q2) and the in-plane axes nq x f are recomputed per pair, after the stages that reject most.
-struct Query {
-    float p[3][3];
-    float lo[3], hi[3];
-    float q1[3], q2[3];
-    float nq[3];
-};
-
-// the query's interval on axis A: q0 = 0 is projected like the others (an infinite A gives the header's NaN)
-__device__ __forceinline__ bool axis_separates(const float A[3], const float v0[3], const float v1[3], const float v2[3], const Query &q)
-{
-    const float zero[3] = {0.0f, 0.0f, 0.0f};
-    const float s0 = dot(A, v0), s1 = dot(A, v1), s2 = dot(A, v2);
-    const float t0 = dot(A, zero), t1 = dot(A, q.q1), t2 = dot(A, q.q2);
-    return min3(s0, s1, s2) > max3(t0, t1, t2) || max3(s0, s1, s2) < min3(t0, t1, t2);
-}
-
-// the header's per-pair test of the scene triangle at `tri` (nine floats)
-__device__ __forceinline__ bool triangle_intersects(const Query &q, bool skip_shared, const float *tri)
-{
-    float a[3], b[3], c[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-        a[j] = tri[j], b[j] = tri[3 + j], c[j] = tri[6 + j];
-    // stage 0: the two vertex boxes, on the untranslated coordinates
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-        if (min3(a[j], b[j], c[j]) > q.hi[j] || max3(a[j], b[j], c[j]) < q.lo[j])
-            return false;
-    if (skip_shared) {
-#pragma unroll
-        for (int i = 0; i < 3; i++)
-            if (same_corner(a, q.p[i]) || same_corner(b, q.p[i]) || same_corner(c, q.p[i]))
-                return false;
-    }
-    const float zero[3] = {0.0f, 0.0f, 0.0f};
-    float v[3][3], e[3][3], f[3][3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        v[0][j] = a[j] - q.p[0][j], v[1][j] = b[j] - q.p[0][j], v[2][j] = c[j] - q.p[0][j];
-        e[0][j] = v[1][j] - v[0][j], e[1][j] = v[2][j] - v[1][j], e[2][j] = v[0][j] - v[2][j];
-        f[0][j] = q.q1[j] - zero[j], f[1][j] = q.q2[j] - q.q1[j], f[2][j] = zero[j] - q.q2[j];
-    }
-    float nt[3];
-    cross(nt, e[0], e[1]);
-    if (all_zero(nt))
-        return false;
-    if (axis_separates(q.nq, v[0], v[1], v[2], q) || axis_separates(nt, v[0], v[1], v[2], q))
-        return false;
-    float A[3];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            cross(A, f[i], e[j]);
-            if (axis_separates(A, v[0], v[1], v[2], q))
-                return false;
-        }
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        cross(A, q.nq, f[i]);
-        if (axis_separates(A, v[0], v[1], v[2], q))
-            return false;
-    }
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        cross(A, nt, e[j]);
-        if (axis_separates(A, v[0], v[1], v[2], q))
-            return false;
-    }
-    return true;
-}
-
-// the walk's cull: the node's box against the query's vertex box, six comparisons of stored floats
-__device__ __forceinline__ bool boxes_overlap(const Box &node, const float lo[3], const float hi[3])
-{
-    return !(node.hi[0] < lo[0] || node.lo[0] > hi[0] || node.hi[1] < lo[1] || node.lo[1] > hi[1] || node.hi[2] < lo[2] ||
-             node.lo[2] > hi[2]);
-}
 
 // One lane per query.  SLOTS: the register slots of the K smallest indices (k <= SLOTS), kSlotsInMemory: they live in the
 // query's output slots (any k, also 0).  ANY: stop at the first member (k is 0).  COUNT: the work counters.
@@ -290,33 +192,18 @@ __global__ void __launch_bounds__(kBlock) intersect_kernel(SceneView sc, Interse
 constexpr Nouns kNouns = {"triangle", "triangles", "scene", "out", "max_triangles", "triangle-intersection query"};
 constexpr uint32_t kKnownFlags = SHRAY_INTERSECT_ANY | SHRAY_INTERSECT_SKIP_SHARED;
 
-int check_params(const shray_intersect_params *op)
-{
-    if (!op)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "intersect params are NULL");
-    if (op->struct_size != sizeof(shray_intersect_params))
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "shray_intersect_params.struct_size is %u, this library expects %zu", op->struct_size,
-                    sizeof(shray_intersect_params));
-    if (op->max_triangles < 0 || op->max_triangles > SHRAY_INTERSECT_MAX || (op->flags & ~kKnownFlags) || op->reserved != 0)
-        return fail(SHRAY_ERR_INVALID_ARGUMENT, "intersect params out of range (max_triangles %d of 0 .. %d, flags 0x%x, reserved %d)",
-                    op->max_triangles, (int)SHRAY_INTERSECT_MAX, op->flags, op->reserved);
-    return SHRAY_OK;
-}
-
 // the checks every form makes before it touches a scene or a device; the self form's `triangles` is its scene (it has no
 // item array) and its `first` the first of the scene's triangles, 0 for the item forms
 int check_query(shray_scene *scene, const shray_intersect_params *op, const void *triangles, int64_t first, int64_t count, const void *out,
                 const void *counts)
 {
-    const int rc = check_params(op);
+    const int rc = check_params(op, kKnownFlags);
     if (rc)
         return rc;
     return check_first_k(kNouns, scene, triangles, count, op->max_triangles, out, counts, [&] {
         if (first < 0)
             return fail(SHRAY_ERR_INVALID_ARGUMENT, "negative first triangle %lld", (long long)first);
-        if ((op->flags & SHRAY_INTERSECT_ANY) && (op->max_triangles != 0 || !counts))
-            return fail(SHRAY_ERR_INVALID_ARGUMENT, "SHRAY_INTERSECT_ANY needs max_triangles 0 (it is %d) and counts", op->max_triangles);
-        return (int)SHRAY_OK;
+        return check_any(op, counts);
     });
 }
 

@@ -2,7 +2,7 @@
 // counted, the nearest K kept in order.
 //
 // One lane per point in one-wave workgroups.  The walk is shaped as the closest-point walk (point/point_walk.h; the box bound
-// and closest_on_triangle both call are point/closest_on_triangle.h: a record here is that function's, not a restatement): the 32-byte records of
+// and closest_on_triangle both call are point/closest_on_triangle.h: a record here is that function's, not a copy's): the 32-byte records of
 // octant copy 7 of the packed tree, the corners from the scene's positions, a stack in LDS, level-major, one entry per edge
 // of the tree's height, nearest child first.  The near set does not depend on the visit order (the header).  The form that is
 // asked for counts skips a node only when its box bound is above max_dist2; the form that is not skips one whose bound is

@@ -1,0 +1,54 @@
+// params_check.h -- the params refusals of include/shader_ray_overlap.h and include/shader_ray_intersect.h, each made by the
+// query's library (overlap/overlap.hip, intersect/intersect.hip) and by its instanced form (instance_overlap/,
+// instance_intersect/): the struct itself, then the misuse of the ANY flag, which a library makes at its own place among its
+// refusals.  Host code only.
+#pragma once
+
+#include "client_internal.h"
+#include "shader_ray_intersect.h"
+#include "shader_ray_overlap.h"
+
+namespace {
+
+inline int check_params(const shray_overlap_params *op)
+{
+    if (!op)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "overlap params are NULL");
+    if (op->struct_size != sizeof(shray_overlap_params))
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "shray_overlap_params.struct_size is %u, this library expects %zu", op->struct_size,
+                    sizeof(shray_overlap_params));
+    if (op->max_triangles < 0 || op->max_triangles > SHRAY_OVERLAP_MAX || (op->flags & ~(uint32_t)SHRAY_OVERLAP_ANY) || op->reserved != 0)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "overlap params out of range (max_triangles %d of 0 .. %d, flags 0x%x, reserved %d)",
+                    op->max_triangles, (int)SHRAY_OVERLAP_MAX, op->flags, op->reserved);
+    return SHRAY_OK;
+}
+
+inline int check_any(const shray_overlap_params *op, const void *counts)
+{
+    if ((op->flags & SHRAY_OVERLAP_ANY) && (op->max_triangles != 0 || !counts))
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "SHRAY_OVERLAP_ANY needs max_triangles 0 (it is %d) and counts", op->max_triangles);
+    return SHRAY_OK;
+}
+
+// `known`: the flags of the form that asks (only the instance form knows SHRAY_INTERSECT_SKIP_OWN_INSTANCE)
+inline int check_params(const shray_intersect_params *op, uint32_t known)
+{
+    if (!op)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "intersect params are NULL");
+    if (op->struct_size != sizeof(shray_intersect_params))
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "shray_intersect_params.struct_size is %u, this library expects %zu", op->struct_size,
+                    sizeof(shray_intersect_params));
+    if (op->max_triangles < 0 || op->max_triangles > SHRAY_INTERSECT_MAX || (op->flags & ~known) || op->reserved != 0)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "intersect params out of range (max_triangles %d of 0 .. %d, flags 0x%x, reserved %d)",
+                    op->max_triangles, (int)SHRAY_INTERSECT_MAX, op->flags, op->reserved);
+    return SHRAY_OK;
+}
+
+inline int check_any(const shray_intersect_params *op, const void *counts)
+{
+    if ((op->flags & SHRAY_INTERSECT_ANY) && (op->max_triangles != 0 || !counts))
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "SHRAY_INTERSECT_ANY needs max_triangles 0 (it is %d) and counts", op->max_triangles);
+    return SHRAY_OK;
+}
+
+}   // namespace
