@@ -29,6 +29,7 @@ OVERLAP_LIB = os.path.join(PKG_DIR, "libshray_overlap.so")
 INSTANCE_OVERLAP_LIB = os.path.join(PKG_DIR, "libshray_instance_overlap.so")
 INTERSECT_LIB = os.path.join(PKG_DIR, "libshray_intersect.so")
 INSTANCE_INTERSECT_LIB = os.path.join(PKG_DIR, "libshray_instance_intersect.so")
+INSTANCE_SDF_LIB = os.path.join(PKG_DIR, "libshray_instance_sdf.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
 HIP_LIB = os.environ.get("SHRAY_HIP_LIB") or os.path.join(PKG_DIR, "libshray_hip.so")
 
@@ -519,6 +520,15 @@ INSTANCE_INTERSECT_SYMBOLS = [
                                            C.c_void_p, C.c_void_p]),
 ]
 
+# include/shader_ray_instance_sdf.h ------------------------------------------------------------------------
+INSTANCE_SDF_SYMBOLS = [
+    ("shray_signed_distance_instances_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p]),
+    ("shray_signed_distance_instances", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("shray_signed_distance_instances_counters", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                           C.POINTER(Counters)]),
+]
+
 _host = None
 _hip = None
 _clients = {}   # path -> the loaded client library of libshray_hip.so
@@ -650,6 +660,12 @@ def load_instance_overlap():
 def load_instance_intersect():
     """Loads the instanced triangle-intersection library (libshray_instance_intersect.so: depends on libshray_instance.so too)."""
     return _load_client(INSTANCE_INTERSECT_LIB, INSTANCE_INTERSECT_SYMBOLS)
+
+
+def load_instance_sdf():
+    """Loads the instanced signed-distance library (libshray_instance_sdf.so: depends on libshray_instance.so,
+    libshray_instance_point.so and libshray_sdf.so too)."""
+    return _load_client(INSTANCE_SDF_LIB, INSTANCE_SDF_SYMBOLS)
 
 
 def check_dist(code: int):

@@ -510,4 +510,23 @@ int shray_scene_sign_data_download(shray_scene *scene, float *out)
     return SHRAY_OK;
 }
 
+// Not in the header: for libshray_instance_sdf.so, which signs in a member scene's object space.  The scene's sign data
+// (SHRAY_SIGN_DATA_FLOATS floats per triangle, device memory of the scene's device) current for work enqueued on
+// `hip_stream` after this call: derived there when it is stale (first use, or after a refit), else that stream waits for the
+// derivation's event.  The pointer stays the scene's own until it is destroyed; a re-derivation rewrites it in place.
+// Host-only; makes the scene's device current and waits for nothing.
+int shrayi_scene_sign_data(shray_scene *scene, void *hip_stream, const float **d_sign)
+{
+    if (!scene || !d_sign)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene or d_sign is NULL");
+    *d_sign = nullptr;
+    ShrayQueryScene q;
+    SdfState *st = nullptr;
+    const int rc = prepare(scene, &q, &st, (hipStream_t)hip_stream, false);
+    if (rc)
+        return rc;
+    *d_sign = st->sign.as<const float>();
+    return SHRAY_OK;
+}
+
 }   // extern "C"

@@ -1268,6 +1268,59 @@ class InstanceSet:
         N.check(N.load_instance_point().shray_closest_points_instances_device(
             self._handle, C.c_void_p(points_ptr), count, C.c_void_p(out_ptr), C.c_void_p(instances_ptr or None), C.c_void_p(stream_ptr)))
 
+    def signed_distance(self, points, max_dist2=None, closest: bool = False, counters: bool = False):
+        """Instanced signed distances (include/shader_ray_instance_sdf.h): per world-space point the distance to the nearest
+        instance's surface (closest_points' record), negative where the point lies inside that instance, the sign decided in
+        the instance's object space with its member scene's pseudonormals; NaN for a point with nothing within its radius.
+        `points` and `max_dist2` as for closest_points.  Host points take the blocking path and return float32 [n]; a float32
+        [n, 3] / [n, 4] GPU tensor on the set's device takes the device path on the current torch stream and returns a float32
+        [n] tensor.  With closest=True returns (values, records, instances), the last two as closest_points returns them.
+        counters=True (host points only) also returns the counters of the sign walks, last."""
+        lib = N.load_instance_sdf()
+        points = _host_if_cpu(points)
+        if _is_torch(points):
+            import torch
+            if counters:
+                raise ValueError("counters are counted on the host path: pass host points")
+            if points.device.index != self.device:
+                raise ValueError(f"points are on {points.device}, the set on cuda:{self.device}")
+            pts = self._scenes[0]._device_points(points, max_dist2)
+            out = torch.empty(len(pts), dtype=torch.float32, device=pts.device)
+            rec = torch.empty((len(pts), 8), dtype=torch.int32, device=pts.device) if closest else None
+            inst = torch.empty(len(pts), dtype=torch.int32, device=pts.device) if closest else None
+            stream = torch.cuda.current_stream(pts.device)
+            N.check(lib.shray_signed_distance_instances_device(
+                self._handle, C.c_void_p(pts.data_ptr()), len(pts), C.c_void_p(out.data_ptr()), C.c_void_p(rec.data_ptr() if closest else None),
+                C.c_void_p(inst.data_ptr() if closest else None), C.c_void_p(stream.cuda_stream)))
+            return (out, rec, inst) if closest else out
+        pts = _host_points(points, max_dist2)
+        out = np.empty(len(pts), np.float32)
+        rec = np.empty(len(pts), CLOSEST_DTYPE) if closest else None
+        inst = np.empty(len(pts), np.int32) if closest else None
+        args = (self._handle, pts.ctypes.data_as(C.c_void_p), len(pts), out.ctypes.data_as(C.c_void_p),
+                rec.ctypes.data_as(C.c_void_p) if closest else None, inst.ctypes.data_as(C.c_void_p) if closest else None)
+        result = (out, rec, inst) if closest else (out,)
+        if counters:
+            c = N.Counters()
+            N.check(lib.shray_signed_distance_instances_counters(*args, C.byref(c)))
+            return result + (c.as_dict(),)
+        N.check(lib.shray_signed_distance_instances(*args))
+        return result if closest else out
+
+    def signed_distance_into(self, points_ptr: int, count: int, out_ptr: int, closest_ptr: int = 0, instances_ptr: int = 0,
+                             stream_ptr: int = 0):
+        """Asynchronous instanced signed distance queries on device memory of the set's device
+        (shray_signed_distance_instances_device): `count` shray_point records at `points_ptr` -> `count` float32 at `out_ptr`,
+        unless `closest_ptr` is 0 `count` shray_closest records there, and unless `instances_ptr` is 0 int32 instance indices
+        there, on a HIP stream (`stream_ptr`)."""
+        N.check(N.load_instance_sdf().shray_signed_distance_instances_device(
+            self._handle, C.c_void_p(points_ptr), count, C.c_void_p(out_ptr), C.c_void_p(closest_ptr or None),
+            C.c_void_p(instances_ptr or None), C.c_void_p(stream_ptr)))
+
+    def closed(self) -> bool:
+        """Whether every member scene is closed (Scene.surface_info()["closed"]): what the sign's guarantee asks of them."""
+        return all(bool(s.surface_info()["closed"]) for s in {id(s): s for s in self._scenes}.values())
+
     def triangles_within(self, points, max_near: int = 8, counts: bool = True, counters: bool = False):
         """Instanced within-radius queries (include/shader_ray_instance_near.h): per world-space point the number of
         (instance, triangle) pairs whose closest point lies within its max_dist2, measured on the instances' triangles mapped
