@@ -110,7 +110,7 @@ def shares_matrix(q, t):
 def restated_walk(corners, maps, queries, order, k, counts, *, skip_shared=False, own=None, skip_own=False, scene_of=None,
                   object_queries=None, node_cull=misses, image_box=IP.image_box, top_boxes=None, top_cull=guarded_misses,
                   key=key_instance_first, skip_slot=0, count_kept_only=False, any_only=False, own_is=same_instance,
-                  shared_on_object=False):
+                  shared_on_object=False, members=None):
     """The kernel's walk, one query at a time: the instances in `order`; an instance that own_is(i, own, scene_of) says is the
     query's own is not walked when skip_own; with `top_boxes` (one (lo, hi) per instance) and more than one instance, an
     instance is entered only when top_cull does not separate its box from the query's vertex box; without counts (and k > 0) a
@@ -120,8 +120,9 @@ def restated_walk(corners, maps, queries, order, k, counts, *, skip_shared=False
     inserted into the sorted K smallest.  `corners` is one [t, 3, 3] array for every instance or a list with one per instance.
     `queries` are world triangles (the instance form passes own_queries' and `own`).  With any_only a query stops at its first
     member (n is 1 or 0).  With shared_on_object the shared-corner rule compares `object_queries` with the object corners (a
-    mutant).  The keyword arguments replace one decision each.  Returns (triangles [n, k], instances [n, k], counts [n] or
-    None, triangle tests, instance walks)."""
+    mutant).  The keyword arguments replace one decision each.  `members`: one bool [n, t] per instance, the brute force's
+    intersect_ref.intersects(queries, world corners) where the caller holds it already.  Returns (triangles [n, k], instances
+    [n, k], counts [n] or None, triangle tests, instance walks)."""
     q = IR.corners_of(queries)
     lo, hi = vertex_box(q)
     n = len(q)
@@ -139,7 +140,7 @@ def restated_walk(corners, maps, queries, order, k, counts, *, skip_shared=False
         M = np.asarray(maps[i], F)
         ilo, ihi = image_box(M, np.stack([nd[0] for nd in tree]), np.stack([nd[1] for nd in tree]))
         world = IP.map_corners(M, mine).reshape(-1, 3, 3)
-        member = IR.intersects(q, world.reshape(-1), False)
+        member = IR.intersects(q, world.reshape(-1), False) if members is None else np.asarray(members[i], bool)
         if skip_shared:
             member = member & ~(shares_matrix(np.asarray(object_queries, F).reshape(-1, 3, 3), np.asarray(mine, F)) if shared_on_object
                                 else shares_matrix(q, world))
