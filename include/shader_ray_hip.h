@@ -359,7 +359,9 @@ int shray_render_counters(shray_scene *scene, const shray_frame_params *params,
  * asks whether anything is hit, fs:516-521) and run a pixel's samples in neighbouring lanes; this entry point
  * renders the frame with THAT instance -- the one a launch of frames_per_launch such frames would select -- and
  * returns ITS tallies: equal to the reference's for metals (no shadow rays), smaller for diffuse materials; the
- * image is the same either way.  bad_hits counts primary / bounce samples that returned the iteration-cap marker. */
+ * image is the same either way.  bad_hits counts primary / bounce samples that returned the iteration-cap marker.
+ * The tallying instances never read the view cache (below): env_lookups and the rest are the work of an uncached frame,
+ * also where the timed launches of that view skip the lookup of their background pixels. */
 int shray_render_counters_timed(shray_scene *scene, const shray_frame_params *params,
                                 int width, int height, int spp, int frames_per_launch,
                                 float *rgba_out_host /* may be NULL */,
@@ -374,6 +376,24 @@ int shray_render_counters_timed(shray_scene *scene, const shray_frame_params *pa
  * *count_out = its length (0: no shape yet, or the identity is still in use); at most `capacity` entries are written.
  * It waits for the device.  The environment variable SHRAY_DISPATCH_ORDER=0 turns the re-ordering off for a process. */
 int shray_scene_dispatch_order(shray_scene *scene, uint32_t *order_out, uint32_t capacity, uint32_t *count_out);
+
+/* View cache ---------------------------------------------------------------- */
+/* What a camera that stands still asks for again in every frame is kept per scene: each pixel's primary direction, and
+ * the colour of a pixel whose primary ray leaves the scene (environment lookup and tone map).  When a whole plain
+ * one-sample frame (spp 1, which 0, no tile set) arrives with a size, camera matrices, image_plane_width, aspect and
+ * tonemap that one of the scene's last launches had (the last two distinct such keys are remembered: a camera that
+ * stands still, or alternates between two positions), the library fills an entry on that launch's stream, and launches
+ * with that key read it from then on; object, light and material may change freely, and a camera that moves every launch
+ * costs a few comparisons on the host.  The frames are bit for bit what they are without it.  Two entries per scene, least
+ * recently used out; an entry takes 28 bytes per pixel (58 MB at 1920x1080) of device memory, and the environment
+ * variable SHRAY_VIEW_CACHE_MAX_MB (default 256) bounds what a scene's entries hold together: larger frames render
+ * uncached.  shray_scene_set_environment drops the entries.  SHRAY_VIEW_CACHE=0 turns the cache off for a process,
+ * shray_scene_set_view_cache(scene, 0) for a scene (its entries are dropped; 1 turns it on again).
+ * Launches of ONE frame never read the cache (a lone frame is latency-bound and measured slower with it).
+ * shray_scene_view_cache_stats: entries filled so far, launches in which at least one frame read an entry, and the
+ * device bytes held now, dropped entries that queued launches may still read included; any pointer may be NULL. */
+int shray_scene_set_view_cache(shray_scene *scene, int on);
+int shray_scene_view_cache_stats(const shray_scene *scene, uint64_t *entries_built, uint64_t *launches_cached, uint64_t *bytes_held);
 
 /* Self-test ---------------------------------------------------------------- */
 /* Runs the kernel's 5-instruction "divide by a per-ray constant" (csrc/exact_div.h)

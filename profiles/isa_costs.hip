@@ -175,6 +175,37 @@ __global__ void cost_primary_and_tonemap(const FrameView *frames, const float *r
     }
 }
 
+// c_pixel's two halves (round 9, the view cache): the primary direction of a one-sample frame's pixel as the frame kernels and
+// the cache's prepass make it (uniform_driver.h: primary_direction) ...
+template <int REPS>
+__global__ void cost_ray_generation(const FrameView *frames, const int *pixels, float *out)
+{
+    const FrameView &fr = frames[0];
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const SharedDivisor by_width = shared_divisor((float)fr.width), by_height = shared_divisor((float)fr.height);
+    const bool eye_in_range = eye_ray_in_range(fr);
+#pragma unroll
+    for (int k = 0; k < REPS; k++) {
+        const int *p = pixels + 2u * i + 1048576u * k;
+        const V3 D = primary_direction(fr, p[0], p[1], 0, 1.0f, by_width, by_height, eye_in_range);
+        float *o = out + 4u * i + 1048576u * k;
+        o[0] = D.x; o[1] = D.y; o[2] = D.z;
+    }
+}
+
+// ... and the tone map of its three channels (fs:527-548)
+template <int REPS>
+__global__ void cost_tonemap(const float *rays, float *out)
+{
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < REPS; k++) {
+        const float *r = rays + 4u * i + 1048576u * k;
+        float *o = out + 4u * i + 1048576u * k;
+        o[0] = filmic(r[0]); o[1] = filmic(r[1]); o[2] = filmic(r[2]);
+    }
+}
+
 #define INSTANTIATE(K, ...)                              \
     template __global__ void K<1>(__VA_ARGS__);          \
     template __global__ void K<2>(__VA_ARGS__);
@@ -186,3 +217,5 @@ INSTANTIATE(cost_shade, SceneView, const FrameView *, const float *, float *)
 INSTANTIATE(cost_traversal_setup, SceneView, const FrameView *, const float *, float *)
 INSTANTIATE(cost_environment, SceneView, const float *, float *)
 INSTANTIATE(cost_primary_and_tonemap, const FrameView *, const float *, float *)
+INSTANTIATE(cost_ray_generation, const FrameView *, const int *, float *)
+INSTANTIATE(cost_tonemap, const float *, float *)

@@ -52,6 +52,10 @@ def measure():
         "c_shade": stage("cost_shade"),
         "c_env": stage("cost_environment"),
         "c_pixel": stage("cost_primary_and_tonemap"),
+        # c_pixel's halves (the view cache removes the first from every cached frame's waves, the second with c_env from the
+        # waves whose primary rays all leave the scene)
+        "c_ray_generation": stage("cost_ray_generation"),
+        "c_tonemap": stage("cost_tonemap"),
         "raw_valu_counts": valu,
         "method": "profiles/isa_costs.hip, VALU count of the REPS = 2 instance minus the REPS = 1 instance of each stage",
     }

@@ -167,6 +167,8 @@ HIP_SYMBOLS = [
     ("shray_render_counters_timed", C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.c_int, C.c_int, C.c_int, C.c_int,
                                               c_float_p, C.POINTER(Counters)]),
     ("shray_scene_dispatch_order", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("shray_scene_set_view_cache", C.c_int, [C.c_void_p, C.c_int]),
+    ("shray_scene_view_cache_stats", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("shray_selftest_division", C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("shray_selftest_reciprocal", C.c_int, [C.POINTER(C.c_uint64)]),
     ("shray_probe_vector_cache", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),

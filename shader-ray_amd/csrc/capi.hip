@@ -163,10 +163,61 @@ struct shray_scene {
     size_t frame_bytes = 0;
     hipStream_t readback_stream = nullptr;
 
+    // View cache: what a fixed camera's frames have in common, kept per scene.  In the viewer a drag turns the object or the
+    // light and only the zoom rewrites the camera, so frame after frame the kernels made the same width * height primary
+    // directions, and for every pixel whose primary ray leaves the scene the same environment lookup and tone map.  An entry
+    // holds both for one ViewKey, per pixel at its row-major output index (kernel_view_cache.hip writes them, with the frame
+    // kernels' own functions: the same bits); the timed one-sample instances read them through FrameView::view_rays / view_sky
+    // (uniform_driver.h).  Only whole plain one-sample frames of kernel 0 are eligible (spp == 1, which == 0, no tile set, no
+    // tallies): every other launch is what it was.
+    // Policy: an entry is built -- one prepass kernel on the launch's own stream, in front of the frame kernel -- when a frame
+    // carries a key that an earlier launch carried lately, and not before: the scene remembers the last kViewEntries distinct
+    // keys (`view_recent`), so a camera that stands still is cached from its second launch on, one that alternates between
+    // two positions from its third and fourth, and one that moves every launch (or cycles through more positions than there
+    // are entries) pays a few key comparisons on the host and nothing else.  kViewEntries entries, least recently used out; an entry larger than
+    // SHRAY_VIEW_CACHE_MAX_MB (default 256; 28 bytes per pixel, 58 MB at 1920x1080) is not built, and the entries together
+    // stay below it.  The launch that builds an entry, and later launches on its stream, use it in stream order; launches on
+    // other streams use it once its `ready` event has been seen complete (polled: no stream waits for another) and until then
+    // carry null pointers -- the frame is the same either way.
+    // An evicted or invalidated entry's buffers are set aside like a dispatch order's (`view_retired`): launches that were
+    // enqueued before may still read them, so they are freed or handed out again only once kBatchSlots further launches have
+    // been enqueued (launch_stack_views' slot wait); nothing synchronises with the device.
+    struct ViewKey {                        // compared as bytes (no padding: 160 bytes)
+        int32_t width, height, spp, tonemap;
+        float camera_matrix[16], camera_normal_matrix[16];
+        float image_plane_width, aspect;
+        uint64_t env_generation;
+    };
+    struct ViewEntry {
+        ViewKey key{};
+        DeviceBuffer rays, sky;             // 3 and 4 floats per pixel
+        size_t pixels = 0;                  // 0: the slot holds no entry
+        hipEvent_t ready = nullptr;         // recorded behind the prepass
+        bool ready_known = false;           // `ready` has been seen complete
+        hipStream_t built_on = nullptr;     // launches enqueued on it afterwards are ordered behind the prepass
+        unsigned long long last_use = 0;    // launch number
+    };
+    struct RetiredView {
+        DeviceBuffer rays, sky;
+        size_t pixels = 0;
+        unsigned long long retired_at = 0;  // the scene's launch number when the entry left
+    };
+    static constexpr int kViewEntries = 2;
+    ViewEntry view_entries[kViewEntries];
+    std::vector<std::unique_ptr<RetiredView>> view_retired;
+    ViewKey view_recent[kViewEntries] = {};  // the last kViewEntries distinct keys that launches carried, most recent first
+    int view_recent_count = 0;
+    bool view_cache_on = true;              // shray_scene_set_view_cache
+    uint64_t env_generation = 0;            // bumped by every environment upload
+    uint64_t view_entries_built = 0, view_launches_cached = 0;   // shray_scene_view_cache_stats
+
     SceneView view{};
 
     ~shray_scene()
     {
+        for (ViewEntry &e : view_entries)
+            if (e.ready)
+                (void)hipEventDestroy(e.ready);
         if (readback_stream)
             (void)hipStreamDestroy(readback_stream);
         if (wf_done)
@@ -601,6 +652,195 @@ int dispatch_slot_start(shray_scene *scene, shray_scene::DispatchOrder &d, const
     return SHRAY_OK;
 }
 
+// The view cache (shray_scene::ViewEntry).  SHRAY_VIEW_CACHE=0 turns it off for a process (read once);
+// shray_scene_set_view_cache for a scene.
+bool view_cache_enabled()
+{
+    static const bool on = [] {
+        const char *e = getenv("SHRAY_VIEW_CACHE");
+        return !(e && e[0] == '0');
+    }();
+    return on;
+}
+// bytes the entries of a scene may hold together (read where an entry is about to be built, not per launch)
+size_t view_cache_cap_bytes()
+{
+    const char *e = getenv("SHRAY_VIEW_CACHE_MAX_MB");
+    const long long mb = e ? atoll(e) : 256;
+    return mb <= 0 ? 0 : (size_t)mb << 20;
+}
+constexpr size_t kViewBytesPerPixel = 7 * sizeof(float);
+
+bool view_cache_eligible(const FrameView &f) { return f.spp == 1 && f.which == 0 && f.tile_stride == 0; }
+
+void view_key_of(const FrameView &f, uint64_t env_generation, shray_scene::ViewKey *key)
+{
+    memset(key, 0, sizeof(*key));
+    key->width = f.width;
+    key->height = f.height;
+    key->spp = f.spp;
+    key->tonemap = f.tonemap;
+    memcpy(key->camera_matrix, f.camera_matrix, sizeof(key->camera_matrix));
+    memcpy(key->camera_normal_matrix, f.camera_normal_matrix, sizeof(key->camera_normal_matrix));
+    key->image_plane_width = f.image_plane_width;
+    key->aspect = f.aspect;
+    key->env_generation = env_generation;
+}
+
+// the entry leaves; launches enqueued so far may still read its buffers
+void view_entry_retire(shray_scene *scene, shray_scene::ViewEntry &e)
+{
+    if (!e.pixels)
+        return;
+    std::unique_ptr<shray_scene::RetiredView> r(new shray_scene::RetiredView);
+    std::swap(r->rays.p, e.rays.p);
+    std::swap(r->sky.p, e.sky.p);
+    r->pixels = e.pixels;
+    r->retired_at = scene->launch_seq;
+    e.pixels = 0;
+    scene->view_retired.push_back(std::move(r));
+}
+
+// A new entry for `key` in launch `seq`: the slot of the least recently used entry that this launch does not read, buffers
+// from the retired ones where one fits.  nullptr: nothing is built (over the cap, no slot, no memory) and the frame renders
+// uncached.
+shray_scene::ViewEntry *view_entry_start(shray_scene *scene, const shray_scene::ViewKey &key, unsigned long long seq, hipStream_t stream)
+{
+    const size_t pixels = (size_t)key.width * (size_t)key.height, cap = view_cache_cap_bytes();
+    if (pixels * kViewBytesPerPixel > cap)
+        return nullptr;
+    shray_scene::ViewEntry *slot = nullptr;
+    for (;;) {
+        size_t held = 0;
+        shray_scene::ViewEntry *lru = nullptr;
+        slot = nullptr;
+        for (shray_scene::ViewEntry &e : scene->view_entries) {
+            held += e.pixels * kViewBytesPerPixel;
+            if (!e.pixels)
+                slot = slot ? slot : &e;
+            else if (e.last_use != seq && (!lru || e.last_use < lru->last_use))
+                lru = &e;
+        }
+        if (slot && held + pixels * kViewBytesPerPixel <= cap)
+            break;
+        if (!lru)
+            return nullptr;
+        view_entry_retire(scene, *lru);
+    }
+    shray_scene::ViewEntry &e = *slot;
+    // retired buffers nobody reads any more: one pair that fits serves this entry, the others are freed
+    for (size_t k = 0; k < scene->view_retired.size();) {
+        shray_scene::RetiredView &r = *scene->view_retired[k];
+        if (seq < r.retired_at + shray_scene::kBatchSlots) {
+            k++;
+            continue;
+        }
+        if (!e.rays.p && r.pixels >= pixels && r.pixels <= pixels + pixels / 4) {
+            std::swap(e.rays.p, r.rays.p);
+            std::swap(e.sky.p, r.sky.p);
+        }
+        scene->view_retired.erase(scene->view_retired.begin() + (long)k);
+    }
+    if (!e.rays.p || !e.sky.p) {
+        e.rays.release();
+        e.sky.release();
+        if (e.rays.reserve(pixels * 3 * sizeof(float)) != hipSuccess || e.sky.reserve(pixels * 4 * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            e.rays.release();
+            e.sky.release();
+            return nullptr;
+        }
+    }
+    if (!e.ready && hipEventCreateWithFlags(&e.ready, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        e.ready = nullptr;
+        e.rays.release();
+        e.sky.release();
+        return nullptr;
+    }
+    e.key = key;
+    e.pixels = pixels;
+    e.ready_known = false;
+    e.built_on = stream;    // (the prepass follows on it, in this launch: view_cache_fill)
+    e.last_use = seq;
+    return &e;
+}
+
+// Gives the frames of launch `seq` their cached tables (staged[k].view_rays / view_sky) and decides which entries the launch
+// builds: build_frame[0 .. *builds) are frames whose entry (build_entry[]) the caller fills, behind the upload of the
+// frames' views and in front of the frame kernel, with view_cache_fill.
+void view_cache_attach(shray_scene *scene, const FrameView *views, int count, FrameView *staged, unsigned long long seq, hipStream_t stream,
+                       int build_frame[shray_scene::kViewEntries], shray_scene::ViewEntry *build_entry[shray_scene::kViewEntries], int *builds)
+{
+    using Key = shray_scene::ViewKey;
+    constexpr int kRecent = shray_scene::kViewEntries;
+    Key recent[kRecent + 1];          // the keys seen lately, most recent first, as they will be after this launch
+    int recent_count = scene->view_recent_count;
+    memcpy(recent, scene->view_recent, sizeof(Key) * (size_t)recent_count);
+    bool used = false;
+    *builds = 0;
+    for (int k = 0; k < count; k++) {
+        if (!view_cache_eligible(views[k]))
+            continue;
+        Key key;
+        view_key_of(views[k], scene->env_generation, &key);
+        {   // move to the front
+            int at = 0;
+            while (at < recent_count && memcmp(&recent[at], &key, sizeof(key)) != 0)
+                at++;
+            if (at == recent_count && recent_count <= kRecent)
+                recent_count++;
+            for (int j = at < recent_count ? at : recent_count - 1; j > 0; j--)
+                recent[j] = recent[j - 1];
+            recent[0] = key;
+            if (recent_count > kRecent)
+                recent_count = kRecent;
+        }
+        shray_scene::ViewEntry *entry = nullptr;
+        for (shray_scene::ViewEntry &e : scene->view_entries)
+            if (e.pixels && memcmp(&e.key, &key, sizeof(key)) == 0)
+                entry = &e;
+        bool fresh = false;
+        if (!entry) {
+            bool seen = false;     // an earlier launch carried this key lately: the camera stands still, or is back
+            for (int j = 0; j < scene->view_recent_count; j++)
+                seen = seen || memcmp(&scene->view_recent[j], &key, sizeof(key)) == 0;
+            if (!seen || *builds >= shray_scene::kViewEntries)
+                continue;
+            entry = view_entry_start(scene, key, seq, stream);
+            if (!entry)
+                continue;
+            build_frame[*builds] = k;
+            build_entry[*builds] = entry;
+            (*builds)++;
+            fresh = true;
+        }
+        if (!fresh && !entry->ready_known && stream != entry->built_on && hipEventQuery(entry->ready) == hipSuccess)
+            entry->ready_known = true;
+        (void)hipGetLastError();   // (hipErrorNotReady is no error of this launch)
+        if (!(fresh || entry->ready_known || stream == entry->built_on))
+            continue;              // still being written on another stream: this frame computes as ever
+        entry->last_use = seq;
+        staged[k].view_rays = SHRAY_VIEW_CACHE_RAYS ? (const float *)entry->rays.p : nullptr;
+        staged[k].view_sky = SHRAY_VIEW_CACHE_SKY ? (const float *)entry->sky.p : nullptr;
+        used = true;
+    }
+    memcpy(scene->view_recent, recent, sizeof(Key) * (size_t)recent_count);
+    scene->view_recent_count = recent_count;
+    if (used)
+        scene->view_launches_cached++;
+}
+
+int view_cache_fill(shray_scene *scene, shray_scene::ViewEntry &e, const FrameView &fr, const FrameView *d_frame, hipStream_t stream)
+{
+    const hipError_t err = launch_view_cache(scene->view, d_frame, fr, (float *)e.rays.p, (float *)e.sky.p, stream);
+    if (err != hipSuccess)
+        return fail(SHRAY_ERR_DEVICE, "view-cache kernel launch failed: %s", hipGetErrorString(err));
+    HIP_TRY(hipEventRecord(e.ready, stream));
+    scene->view_entries_built++;
+    return SHRAY_OK;
+}
+
 int launch_stack_views(shray_scene *scene, const FrameView *views, int count, float4 *d_out, size_t frame_stride,
                        hipStream_t stream, DeviceCounters *tally = nullptr, int policy_frames = 0, bool tally_full_walk = false)
 {
@@ -688,7 +928,27 @@ int launch_stack_views(shray_scene *scene, const FrameView *views, int count, fl
             }
         }
     }
-    HIP_TRY(hipMemcpyAsync(d_views, staged, sizeof(FrameView) * (size_t)count, hipMemcpyHostToDevice, stream));
+    // the view cache: whole plain one-sample frames of the stack kernel's timed instances (the tallying twins never get the
+    // tables: their tallies stay the work of an uncached frame)
+    int view_build_frame[shray_scene::kViewEntries], view_builds = 0;
+    shray_scene::ViewEntry *view_build_entry[shray_scene::kViewEntries];
+    // Launches of several frames only.  A lone frame is bound by the latency of its longest waves, not by instructions: with the
+    // tables its waves begin with a scalar load and a dependent read of memory no earlier wave of the launch has touched, and
+    // the frame was 1.4-2 % SLOWER (0.385 against 0.378-0.380 ms, R9.1); a one-frame launch is what it was.
+    if (count > 1 && scene->kernel_id == 0 && !tally && scene->view_cache_on && view_cache_enabled())
+        view_cache_attach(scene, views, count, staged, seq, stream, view_build_frame, view_build_entry, &view_builds);
+    hipError_t staged_up = hipMemcpyAsync(d_views, staged, sizeof(FrameView) * (size_t)count, hipMemcpyHostToDevice, stream);
+    for (int k = 0; k < view_builds; k++) {
+        const int rc = staged_up == hipSuccess ? view_cache_fill(scene, *view_build_entry[k], views[view_build_frame[k]], d_views + view_build_frame[k], stream)
+                                               : SHRAY_ERR_DEVICE;
+        if (rc) {
+            for (int j = k; j < view_builds; j++)       // never filled: no later launch may find them
+                view_entry_retire(scene, *view_build_entry[j]);
+            if (staged_up == hipSuccess)
+                return rc;
+        }
+    }
+    HIP_TRY(staged_up);
     bool all_metal = true;
     for (int k = 0; k < count; k++)
         all_metal = all_metal && !(views[k].diffuse_color[0] > 0.0f && views[k].diffuse_color[1] > 0.0f &&
@@ -1314,6 +1574,11 @@ int shray_scene_set_environment_storage(shray_scene *scene, const float *rgb, in
         w = nw;
         h = nh;
     }
+    // the view cache's entries hold lookups in the old environment: their keys no longer match anything
+    scene->env_generation++;
+    for (shray_scene::ViewEntry &e : scene->view_entries)
+        view_entry_retire(scene, e);
+    scene->view_recent_count = 0;
     HIP_TRY(scene->env.upload(pyramid.data(), pyramid.size() * sizeof(float)));
     scene->view.env = (const float *)scene->env.p;
     scene->view.env_w = width;
@@ -1431,6 +1696,38 @@ int shray_scene_set_kernel(shray_scene *scene, int kernel_id)
         return fail(SHRAY_ERR_BAD_TREE, "the scene's hit/miss tables are not a canonical threaded tree; only the "
                     "literal threaded kernel (1) can run it");
     scene->kernel_id = kernel_id;
+    return SHRAY_OK;
+}
+
+int shray_scene_set_view_cache(shray_scene *scene, int on)
+{
+    if (!scene)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene is NULL");
+    scene->view_cache_on = on != 0;
+    if (!on) {
+        for (shray_scene::ViewEntry &e : scene->view_entries)
+            view_entry_retire(scene, e);
+        scene->view_recent_count = 0;
+    }
+    return SHRAY_OK;
+}
+
+int shray_scene_view_cache_stats(const shray_scene *scene, uint64_t *entries_built, uint64_t *launches_cached, uint64_t *bytes_held)
+{
+    if (!scene)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene is NULL");
+    if (entries_built)
+        *entries_built = scene->view_entries_built;
+    if (launches_cached)
+        *launches_cached = scene->view_launches_cached;
+    if (bytes_held) {
+        size_t pixels = 0;
+        for (const shray_scene::ViewEntry &e : scene->view_entries)
+            pixels += e.pixels;
+        for (const auto &r : scene->view_retired)
+            pixels += r->pixels;
+        *bytes_held = (uint64_t)(pixels * kViewBytesPerPixel);
+    }
     return SHRAY_OK;
 }
 

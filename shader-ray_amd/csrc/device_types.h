@@ -3,6 +3,19 @@
 
 #include <stdint.h>
 
+// The view cache's two halves (FrameView::view_rays, view_sky) in the timed one-sample instances.  0 compiles a half's reads
+// out of the kernels and leaves its pointer null (A/B builds): cached primary directions, cached background pixels
+#ifndef SHRAY_VIEW_CACHE_RAYS
+#define SHRAY_VIEW_CACHE_RAYS 1
+#endif
+#ifndef SHRAY_VIEW_CACHE_SKY
+#define SHRAY_VIEW_CACHE_SKY 1
+#endif
+// 1: the kernels read the two tables with the non-temporal hint (measured: R9.1)
+#ifndef SHRAY_VIEW_CACHE_NT
+#define SHRAY_VIEW_CACHE_NT 0
+#endif
+
 namespace shray {
 
 // Scene arrays resident in HBM.
@@ -82,6 +95,12 @@ struct FrameView {
     // dispatch_order[k] (nullptr = k), and every wave leaves how long it ran in dispatch_cost[patch] (nullptr = not asked)
     const uint32_t *dispatch_order;
     uint32_t *dispatch_cost;
+    // the scene's view cache (capi.hip: ViewCache; kernel_view_cache.hip fills the tables): per pixel of a whole one-sample
+    // frame, at its row-major output index, the primary ray's world-space direction (three floats) and the RGBA a pixel
+    // stores when that ray leaves the scene (four floats, read as one float4).  nullptr = not cached: the timed one-sample
+    // instances compute both as ever; no other instance reads the two
+    const float *view_rays;
+    const float *view_sky;
 };
 
 // SHRAY_DISPATCH_ORDER (1): heaviest patches first in the convergent batch kernels (capi.hip: DispatchOrder); 0 compiles

@@ -53,6 +53,10 @@ hipError_t launch_wavefront(const SceneView &sc, const FrameView *d_view, const 
 // bulk_class: classes from this one on (costs below (16 - bulk_class) / 16 of the largest) count as one.
 hipError_t launch_dispatch_order(uint32_t *cost, uint32_t *order, uint32_t n, hipStream_t stream, int bulk_class);
 
+// The view cache's prepass (kernel_view_cache.hip): fills rays[3 * width * height] and sky[4 * width * height] for the whole
+// one-sample frame `fr`, whose view in device memory is d_frame.
+hipError_t launch_view_cache(const SceneView &sc, const FrameView *d_frame, const FrameView &fr, float *rays, float *sky, hipStream_t stream);
+
 // rank 0's de-interleave (kernel_assemble.hip); strides in floats: rank_stride between ranks' buffers,
 // frame_stride between a rank's consecutive frames
 // (c0, c1): phases per period owned by rank 0 / by every other rank (1, 1 = even split)

@@ -51,6 +51,30 @@ __device__ __forceinline__ V3 unit_of_eye(V3 a, bool components_in_range)
     return mk(div_by_constant4(a.x, length, y, yl), div_by_constant4(a.y, length, y, yl), div_by_constant4(a.z, length, y, yl));
 }
 
+// The world-space direction of sample s of pixel (px, py): vs:39-60 and fs:619 with the sub-pixel pattern of the oracle.  fn = the
+// frame's sample count as a float; by_width, by_height, eye_in_range: the launch's shared divisors and range test, made once by the
+// caller.  The frame kernels and the view cache's prepass (kernel_view_cache.hip) both call THIS function, and that is the whole
+// parity argument for the cached directions: every operation in it is a single correctly rounded IEEE operation
+// (-ffp-contract=off -fno-fast-math, correctly rounded division and square root), the two wave-uniform branches in it
+// (divide_by_shared, unit_of_eye) choose between forms that give the same quotient in every lane where both apply, and nothing
+// else depends on which lanes share a wave -- so the same source gives the same bits in either kernel, whatever the grid.
+__device__ __forceinline__ V3 primary_direction(const FrameView &fr, int px, int py, int s, float fn, const SharedDivisor &by_width,
+                                                const SharedDivisor &by_height, bool eye_in_range)
+{
+    const float ox = ((float)s + 0.5f) / fn;
+    const float oy = (float)__brev((unsigned int)s) * 2.3283064365386963e-10f + 0.5f / fn;
+    const float u = divide_by_shared((float)px + ox, by_width);
+    const float v = divide_by_shared((float)py + oy, by_height);
+    const V3 eye = unit_of_eye(mk(fr.image_plane_width * (u - 0.5f), fr.image_plane_width * (v - 0.5f) * fr.aspect, -1.0f), eye_in_range);
+    return unit(xform(fr.camera_normal_matrix, eye, 0.0f));
+}
+// the eye ray's normalization: its length is at least 1 (the -1 component) and its components are 0 or no smaller than
+// 2^-85 when the image plane's width and the aspect ratio are ordinary numbers (u - 0.5 is 0 or at least 2^-25)
+__device__ __forceinline__ bool eye_ray_in_range(const FrameView &fr)
+{
+    return magnitude_in(fr.image_plane_width, -30, 8) && magnitude_in(fr.aspect, -30, 8);
+}
+
 // The sample loop's `accumulated`, `modulation` and channel sums between traversals: registers.  (-DSHRAY_PARK=1 keeps them in the
 // wave's spare LDS instead -- variants/parked_state.h: built, bit-identical, 1 % slower, R5.2 -- behind the same interface.)
 #ifndef SHRAY_PARK
@@ -167,9 +191,18 @@ __device__ __forceinline__ void trace_pixels_uniform(const SceneView &sc, const 
     // the pixel coordinates' divisions by the frame's width and height (vs:39-60): dividends px + ox, py + oy are 0 or of
     // magnitude in [2^-25, 2^25) -- a pixel index plus an offset in (0, 1] --, the divisors shared by the whole launch
     const SharedDivisor by_width = shared_divisor(fw), by_height = shared_divisor(fh);
-    // the eye ray's normalization: its length is at least 1 (the -1 component) and its components are 0 or no smaller than
-    // 2^-85 when the image plane's width and the aspect ratio are ordinary numbers (u - 0.5 is 0 or at least 2^-25)
-    const bool eye_in_range = magnitude_in(fr.image_plane_width, -30, 8) && magnitude_in(fr.aspect, -30, 8);
+    const bool eye_in_range = eye_ray_in_range(fr);
+    // The scene's view cache (capi.hip: ViewCache): the timed one-sample instances of the one-wave form read a cached frame's
+    // primary directions instead of making them, and a wave whose 64 primary rays all leave the scene stores the cached
+    // background pixels instead of looking the environment up.  The two pointers are read from `fr` where they are used, never
+    // carried through a traversal.  The background case is a flag and a second arm of the store, NOT an early exit: with a
+    // `return` behind the first traversal the register allocator gave the dense instance 60 bytes of scratch instead of 16
+    // (R9.1); as written it has 12.
+    // (Not the ORDERED instances: they run one-frame launches and tile sets, which never get the tables -- capi.hip -- and a lone
+    // frame was 0.6 % slower for the two tests of the pointers alone.)
+    constexpr bool VIEW_RAYS = SHRAY_VIEW_CACHE_RAYS && !COUNT && !ORDERED && ONE_SAMPLE && Traversal::block_size == 64;
+    constexpr bool VIEW_SKY = SHRAY_VIEW_CACHE_SKY && !COUNT && !ORDERED && ONE_SAMPLE && Traversal::block_size == 64;
+    bool all_sky = false;   // (uniform) every primary ray of the wave has left the scene and the frame's background is cached
 
     V3 sum = mk(0, 0, 0);
     // sample lanes: this lane's colour channel (lane 0 of a pair: also blue) -- and, in the same object, the sample's
@@ -180,20 +213,30 @@ __device__ __forceinline__ void trace_pixels_uniform(const SceneView &sc, const 
         const LanePixel at = s0 == 0 ? first : locate(true);
         const int s = s0 + (int)at.sub;
         const bool has_sample = at.inside && s < samples;
-        // primary ray (vs:39-60, fs:619), sub-pixel pattern of the oracle
-        const float ox = ((float)s + 0.5f) / fn;
-        const float oy = (float)__brev((unsigned int)s) * 2.3283064365386963e-10f + 0.5f / fn;
-        const float u = divide_by_shared((float)at.px + ox, by_width);
-        const float v = divide_by_shared((float)at.py + oy, by_height);
-        const V3 eye = unit_of_eye(mk(fr.image_plane_width * (u - 0.5f), fr.image_plane_width * (v - 0.5f) * fr.aspect, -1.0f), eye_in_range);
+        // primary ray (vs:39-60, fs:619), sub-pixel pattern of the oracle: made here, or the bits the prepass made by the same
+        // function (lanes outside the frame carry no ray: any direction serves)
         V3 P = xform(fr.camera_matrix, mk(0, 0, 0), 1.0f);
-        V3 D = unit(xform(fr.camera_normal_matrix, eye, 0.0f));
+        V3 D = mk(0.0f, 0.0f, -1.0f);
+        const float *cached_rays = VIEW_RAYS ? fr.view_rays : nullptr;
+        if (VIEW_RAYS && cached_rays) {                           // uniform
+            if (at.inside) {
+                const float *d = cached_rays + 3u * at.out_index;
+#if SHRAY_VIEW_CACHE_NT
+                D = mk(__builtin_nontemporal_load(d), __builtin_nontemporal_load(d + 1), __builtin_nontemporal_load(d + 2));
+#else
+                D = mk(d[0], d[1], d[2]);
+#endif
+            }
+        } else {
+            D = primary_direction(fr, at.px, at.py, s, fn, by_width, by_height, eye_in_range);
+        }
 
         kept.set_accumulated(mk(0, 0, 0));
         kept.set_modulation(mk(1, 1, 1));
         bool alive = has_sample;  // still inside trace()'s bounce loop
         bool marker = false;      // returned the bad-hit colour (fs:566-568): no environment term
-        for (int bounce = 0; bounce < fr.bounce_count; bounce++) {
+        int bounce = 0;
+        for (; bounce < fr.bounce_count; bounce++) {
             Hit hit{kFar, -1.0f, 0.0f, 0.0f};
             const int traced = pool.template closest<COUNT>(sc, fr, alive, xform(fr.object_matrix, P, 1.0f),
                                                             xform(fr.object_normal_matrix, D, 0.0f), hit, rc);
@@ -254,8 +297,14 @@ __device__ __forceinline__ void trace_pixels_uniform(const SceneView &sc, const 
                 D = R;
             }
         }
+        // The loop has left in front of its second traversal, or bounce_count is 1.  If no lane is alive now, none hit anything in
+        // the first traversal (a lane that had would have been alive for the second); if none is marked either (a capped lane keeps
+        // its colour on today's path), every primary ray of the wave has left the scene: each pixel is
+        // filmic(0 + 1 * environment(D)) of its own primary direction, which the prepass stored.
+        if (VIEW_SKY && bounce == 1 && fr.view_sky && __builtin_amdgcn_ballot_w64(alive || marker) == 0ull)   // uniform
+            all_sky = true;
         V3 radiance = mk(1.0f, 0.0f, 0.0f);
-        if (has_sample && !marker) {
+        if (has_sample && !marker && !(VIEW_SKY && all_sky)) {
             if (COUNT)
                 rc.env_lookups++;
             const V3 sky = environment(sc, D);
@@ -307,11 +356,26 @@ __device__ __forceinline__ void trace_pixels_uniform(const SceneView &sc, const 
                                                         __uint_as_float(lds[128u + threadIdx.x]), 1.0f)
                                           : make_float4(0, 0, 0, 0);
     } else {
-        V3 result = (ONE_SAMPLE || fr.spp == 1) ? sum : sum / fn;
-        if (fr.tonemap)
-            result = mk(filmic(result.x), filmic(result.y), filmic(result.z));
-        if (me.store)
-            out[me.out_index] = me.inside ? make_float4(result.x, result.y, result.z, 1.0f) : make_float4(0, 0, 0, 0);
+        if (VIEW_SKY && all_sky) {
+            float4 cached = make_float4(0, 0, 0, 0);
+            if (me.inside) {
+#if SHRAY_VIEW_CACHE_NT
+                typedef float native4 __attribute__((ext_vector_type(4)));
+                const native4 c = __builtin_nontemporal_load(reinterpret_cast<const native4 *>(fr.view_sky) + me.out_index);
+                cached = make_float4(c.x, c.y, c.z, c.w);
+#else
+                cached = reinterpret_cast<const float4 *>(fr.view_sky)[me.out_index];
+#endif
+            }
+            if (me.store)
+                out[me.out_index] = cached;
+        } else {
+            V3 result = (ONE_SAMPLE || fr.spp == 1) ? sum : sum / fn;
+            if (fr.tonemap)
+                result = mk(filmic(result.x), filmic(result.y), filmic(result.z));
+            if (me.store)
+                out[me.out_index] = me.inside ? make_float4(result.x, result.y, result.z, 1.0f) : make_float4(0, 0, 0, 0);
+        }
     }
     if (ORDERED && fr.dispatch_cost && (threadIdx.x & 63u) == 0u) {
         // the wave's running time in units of 64 shader-clock ticks (32-bit difference: good for 1.7 s): its patch keeps the

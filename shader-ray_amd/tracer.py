@@ -127,6 +127,16 @@ class Scene:
             N.check(self._lib.shray_scene_dispatch_order(self._handle, out.ctypes.data_as(C.POINTER(C.c_uint32)), n.value, C.byref(n)))
         return out
 
+    def set_view_cache(self, on: bool):
+        """Turns the scene's view cache on or off (shray_scene_set_view_cache); off drops its entries."""
+        N.check(self._lib.shray_scene_set_view_cache(self._handle, 1 if on else 0))
+
+    def view_cache_stats(self) -> dict:
+        """{"entries_built", "launches_cached", "bytes_held"} of the scene's view cache (shray_scene_view_cache_stats)."""
+        built, cached, held = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        N.check(self._lib.shray_scene_view_cache_stats(self._handle, C.byref(built), C.byref(cached), C.byref(held)))
+        return {"entries_built": built.value, "launches_cached": cached.value, "bytes_held": held.value}
+
     def render_into(self, params: N.FrameParams, width: int, height: int, spp: int, out_ptr: int,
                     stream_ptr: int = 0, tiles: N.TileSet | None = None):
         """Asynchronous render into device memory (`out_ptr`, e.g. tensor.data_ptr()) on a
