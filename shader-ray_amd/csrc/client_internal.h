@@ -52,16 +52,7 @@ struct DeviceBuffer {
 
 inline bool aligned(const void *p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1u)) == 0; }
 
-// `device` made current unless it is (a scene's or a set's buffers live on its device)
-inline int use_device(int device)
-{
-    int current = -1;
-    if (hipGetDevice(&current) != hipSuccess || current != device)
-        HIP_TRY(hipSetDevice(device));
-    return SHRAY_OK;
-}
-
-// the scene's query view, on its device
+// the scene's query view, on its device (use_device: error_internal.h)
 inline int enter_scene(shray_scene *scene, ShrayQueryScene *q)
 {
     if (!scene)

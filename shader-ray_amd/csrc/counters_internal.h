@@ -1,4 +1,4 @@
-// counters_internal.h -- the host's sum of the kCounterShards tallies a counting kernel leaves (device_types.h), for capi.hip's
+// counters_internal.h -- the host's sum of the kCounterShards tallies a counting kernel leaves (device_types.h), for render_api.hip's
 // counting renders and the client libraries' blocking forms (client_internal.h).  Host-only, internal to the libraries; not
 // part of the C ABI.
 #pragma once

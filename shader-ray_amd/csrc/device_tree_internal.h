@@ -1,4 +1,4 @@
-// device_tree_internal.h -- what flatten.hip and capi.hip read of the objects bvh_build.hip and flatten.hip keep on the device
+// device_tree_internal.h -- what flatten.hip and scene_create.hip read of the objects bvh_build.hip and flatten.hip keep on the device
 // (the device-resident scene pipeline: shray_bvh_build_device -> shray_flatten_device_tree -> shray_scene_create_from_device).
 // Internal to libshray_hip.so: plain structs of device pointers, filled by two functions that are not part of the C ABI.
 #pragma once

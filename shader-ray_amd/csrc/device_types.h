@@ -91,11 +91,11 @@ struct FrameView {
     // multi-sample frames in the convergent batch kernel: a pixel's samples run in 2^sample_log_x x 2^sample_log_y
     // neighbouring lanes of a wave (uniform_driver.h); 0, 0 = one lane per pixel
     uint32_t sample_log_x, sample_log_y;
-    // dispatch order of the convergent batch kernels (capi.hip: DispatchOrder): the launch's k-th patch slot renders patch
+    // dispatch order of the convergent batch kernels (dispatch_order.h: DispatchOrder): the launch's k-th patch slot renders patch
     // dispatch_order[k] (nullptr = k), and every wave leaves how long it ran in dispatch_cost[patch] (nullptr = not asked)
     const uint32_t *dispatch_order;
     uint32_t *dispatch_cost;
-    // the scene's view cache (capi.hip: ViewCache; kernel_view_cache.hip fills the tables): per pixel of a whole one-sample
+    // the scene's view cache (view_cache.h; kernel_view_cache.hip fills the tables): per pixel of a whole one-sample
     // frame, at its row-major output index, the primary ray's world-space direction (three floats) and the RGBA a pixel
     // stores when that ray leaves the scene (four floats, read as one float4).  nullptr = not cached: the timed one-sample
     // instances compute both as ever; no other instance reads the two
@@ -103,7 +103,16 @@ struct FrameView {
     const float *view_sky;
 };
 
-// SHRAY_DISPATCH_ORDER (1): heaviest patches first in the convergent batch kernels (capi.hip: DispatchOrder); 0 compiles
+// what the host asks of a frame when it picks a kernel instance: its diffuse colour is zero in some component (the instances
+// without the diffuse branch), it is none of the shader's debug / reference views
+inline bool metal(const FrameView &fr)
+{
+    return !(fr.diffuse_color[0] > 0.0f && fr.diffuse_color[1] > 0.0f && fr.diffuse_color[2] > 0.0f);
+}
+inline bool plain_view(int which) { return !(which == 1 || which == 2 || which == 3 || which == 5); }
+inline bool plain_view(const FrameView &fr) { return plain_view(fr.which); }
+
+// SHRAY_DISPATCH_ORDER (1): heaviest patches first in the convergent batch kernels (dispatch_order.h: DispatchOrder); 0 compiles
 // the waves' part of it out (A/B builds)
 
 struct DeviceCounters {

@@ -1,6 +1,7 @@
 // error_internal.h -- how libshray_hip.so and its client libraries (libshray_query.so, libshray_refit.so, libshray_instance.so,
 // libshray_point.so) report an error: the message goes to shray_last_error() (capi.hip keeps it, per thread) and the code is
-// returned.  Host-only, internal to the libraries; not part of the C ABI.
+// returned; and the device switch their entry points begin with, which reports its failure that way.  Host-only, internal to
+// the libraries; not part of the C ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,3 +36,16 @@ __attribute__((format(printf, 2, 3))) inline int fail(int code, const char *fmt,
             return fail(e_ == hipErrorOutOfMemory ? SHRAY_ERR_OUT_OF_MEMORY : SHRAY_ERR_DEVICE, "%s failed: %s", #expr, \
                         hipGetErrorString(e_));                                                                        \
     } while (0)
+
+namespace {
+
+// `device` made current unless it is (a scene's or a set's buffers live on its device)
+inline int use_device(int device)
+{
+    int current = -1;
+    if (hipGetDevice(&current) != hipSuccess || current != device)
+        HIP_TRY(hipSetDevice(device));
+    return SHRAY_OK;
+}
+
+}   // namespace

@@ -1,4 +1,4 @@
-// half_bits.h -- binary32 -> binary16 conversion of the scene's normals, shared by scene creation (capi.hip) and the refit
+// half_bits.h -- binary32 -> binary16 conversion of the scene's normals, shared by scene creation (scene_create.hip) and the refit
 // (refit/refit.hip) so that both produce the same fp16 normals bit for bit.
 #pragma once
 

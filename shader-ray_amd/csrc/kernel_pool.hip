@@ -55,7 +55,7 @@ static bool pool_metal(const FrameView &fr)
     return !(fr.diffuse_color[0] > 0.0f && fr.diffuse_color[1] > 0.0f && fr.diffuse_color[2] > 0.0f);
 }
 
-// which == 0 frames only (the launcher in capi.hip sends the shader's debug views to the stack kernel)
+// which == 0 frames only (the launcher in render_api.hip sends the shader's debug views to the stack kernel)
 hipError_t launch_pool(const SceneView &sc, const FrameView &fr, float4 *out, DeviceCounters *counters, hipStream_t stream,
                        int stack_levels)
 {

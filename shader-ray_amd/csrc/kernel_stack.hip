@@ -45,7 +45,7 @@ __global__ void __launch_bounds__(kBlock, SHRAY_MIN_WAVES_VIEW) trace_stack_view
 }
 
 // `all_metal`: every frame of the batch has a zero diffuse colour; `all_plain`: every frame has which == 0;
-// `deal`: the dealt leaf stage instead of the plain one (capi.hip: leaf_stage_policy)
+// `deal`: the dealt leaf stage instead of the plain one (render_api.hip: leaf_stage_policy)
 hipError_t launch_stack_batch(const SceneView &sc, const FrameView *d_frames, int count, const FrameView &first, bool all_metal,
                               bool all_plain, bool deal, float4 *out, size_t frame_stride, hipStream_t stream, int stack_levels,
                               DeviceCounters *tally, bool pair, bool tally_full_walk, bool ordered)
@@ -98,7 +98,7 @@ hipError_t launch_stack_batch(const SceneView &sc, const FrameView *d_frames, in
 
 // One frame per launch WITH per-ray work tallies: the counting twins (plain frames: one lane per pixel, every shadow ray
 // walked to its end -- the reference's traversals, equal to the CPU oracle's counters) and the debug views.  Launches
-// without tallies never come here: they are batches of one (capi.hip: launch -> launch_stack_views).
+// without tallies never come here: they are batches of one (render_api.hip: launch -> launch_stack_views).
 hipError_t launch_stack(const SceneView &sc, const FrameView &fr, float4 *out, DeviceCounters *counters,
                         hipStream_t stream, int stack_levels)
 {

@@ -1,6 +1,6 @@
 // kernel_stack_batch.hip -- kernel id 0, the timed instances: `count` frames per launch, one-wave workgroups, the
 // convergent driver (uniform_driver.h) over the per-ray LDS stack (stack_traversal.h).  Which instance a launch runs:
-// capi.hip (leaf_stage_policy, DispatchOrder) and launch_stack_batch (kernel_stack.hip).
+// render_api.hip (leaf_stage_policy), dispatch_order.hip and launch_stack_batch (kernel_stack.hip).
 #include "kernel_stack_common.h"
 
 namespace shray {
@@ -27,7 +27,7 @@ __global__ void __launch_bounds__(kBatchBlock, SHRAY_MIN_WAVES_DEALT_DENSE)
     stack_batch_body<true, true, true, 0, false>(sc, frames, out, frame_stride, stack_levels, frame_count_arg, nullptr);
 }
 
-// The zero-diffuse dealing instances once more for launches that read a dispatch order (capi.hip: DispatchOrder -- lone
+// The zero-diffuse dealing instances once more for launches that read a dispatch order (dispatch_order.h: DispatchOrder -- lone
 // frames, tile sets): DENSE = the seven-wave dealt instance of the throughput form (ONE_SAMPLE, DEAL).  Instances of their
 // own because the two scalars an ordered launch carries through the kernel cost the others 2 % (R3.9).
 template <bool ONE_SAMPLE, bool DEAL, bool DENSE>
@@ -43,7 +43,7 @@ void launch_stack_batch_timed(const SceneView &sc, const BatchLaunch &b)
 {
     const bool one = b.one, metallic = b.metallic, deal = b.deal;
 #define SHRAY_LAUNCH_BATCH(K) hipLaunchKernelGGL((K), b.grid, b.block, b.lds_bytes, b.stream, sc, b.d_frames, b.out, b.frame_stride, b.stack_levels, b.count)
-    // `ordered` (capi.hip: DispatchOrder; zero-diffuse launches only): the instances that read a dispatch order
+    // `ordered` (dispatch_order.h: DispatchOrder; zero-diffuse launches only): the instances that read a dispatch order
     if (b.ordered && metallic && b.dense)
         SHRAY_LAUNCH_BATCH((trace_stack_batch_ordered_kernel<true, true, true>));
     else if (b.ordered && metallic && one && deal)
@@ -53,7 +53,7 @@ void launch_stack_batch_timed(const SceneView &sc, const BatchLaunch &b)
     // the throughput form of the headline workload deals its leaves at its own occupancy
     else if (b.dense)
         SHRAY_LAUNCH_BATCH(trace_stack_batch_dense_kernel);
-    // `deal` (capi.hip: leaf_stage_policy) selects the leaf stage of each class of instances
+    // `deal` (render_api.hip: leaf_stage_policy) selects the leaf stage of each class of instances
     else if (one && metallic)
         SHRAY_LAUNCH_BATCH((trace_stack_batch_kernel<true, true, true>));
     else if (one && !deal)

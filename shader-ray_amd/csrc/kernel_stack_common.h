@@ -67,12 +67,7 @@ constexpr int min_waves(bool metal, bool deal, bool one_sample = true)
                          : (one_sample ? SHRAY_MIN_WAVES_GENERAL_PLAIN : SHRAY_MIN_WAVES_GENERAL_PLAIN_MULTI));
 }
 
-inline bool one_sample(const FrameView &fr) { return fr.spp == 1; }
-inline bool metal(const FrameView &fr)
-{
-    return !(fr.diffuse_color[0] > 0.0f && fr.diffuse_color[1] > 0.0f && fr.diffuse_color[2] > 0.0f);
-}
-inline bool plain_view(const FrameView &fr) { return !(fr.which == 1 || fr.which == 2 || fr.which == 3 || fr.which == 5); }
+inline bool one_sample(const FrameView &fr) { return fr.spp == 1; }   // (metal, plain_view: device_types.h)
 
 #ifndef SHRAY_LDS_PAD
 #define SHRAY_LDS_PAD 0u   // unused LDS per wave (occupancy experiments)
@@ -112,7 +107,7 @@ __device__ __forceinline__ StackTraversal<BLOCK, DEAL, PAIR, CACHE, ROOMY> make_
 // DEAL: the dealt leaf stage (leaf_stage.h) instead of the plain leaf loop.
 // TALLY: 0 = the timed kernels; 1 = the same form with per-ray work tallies (what the timed form does); 2 = tallies of
 // the reference's walk (one lane per pixel, every shadow ray to its end) -- the counting twin of the pair traversal.
-// PAIR: both children of a node per turn (variants/pair_traversal.h).  ORDERED: the launch reads a dispatch order (capi.hip).
+// PAIR: both children of a node per turn (variants/pair_traversal.h).  ORDERED: the launch reads a dispatch order (dispatch_order.h).
 // ROOMY: the kernel is compiled for six waves per SIMD (stack_traversal.h).
 template <bool ONE_SAMPLE, bool METAL, bool DEAL, int TALLY, bool PAIR, bool ORDERED = false, bool ROOMY = false>
 __device__ __forceinline__ void stack_batch_body(const SceneView &sc, const FrameView *__restrict__ frames, float4 *out, size_t frame_stride,

@@ -1,4 +1,4 @@
-// kernel_view_cache.hip -- the prepass that fills one entry of a scene's view cache (capi.hip: ViewCache): for every pixel
+// kernel_view_cache.hip -- the prepass that fills one entry of a scene's view cache (view_cache.h): for every pixel
 // of a whole one-sample frame, at its row-major output index,
 //   rays  the primary ray's world-space direction, by uniform_driver.h's primary_direction -- the function the frame kernels call;
 //   sky   what the frame kernels store for a pixel whose primary ray leaves the scene: the environment lookup with its

@@ -186,7 +186,7 @@ __global__ void __launch_bounds__(256) wavefront_resolve_kernel(const FrameView 
     out[p] = make_float4(result.x, result.y, result.z, 1.0f);
 }
 
-// d_view: the frame's view in device memory; scratch: queues / counts / radiance (capi.hip sizes them)
+// d_view: the frame's view in device memory; scratch: queues / counts / radiance (render_api.hip sizes them)
 hipError_t launch_wavefront(const SceneView &sc, const FrameView *d_view, const FrameView &fr, bool metal, PathState *queue0, PathState *queue1,
                             unsigned int *counts, float4 *radiance, float4 *out, hipStream_t stream, int stack_levels)
 {

@@ -58,7 +58,7 @@ __device__ __forceinline__ void leaf_cache_fill(const SceneView &sc, const LaneT
                 at = (uint32_t)n;   // (the slot's number: an inline constant; its byte offset below)
             now = now || same;
             todo = todo && !same;
-            // whatever lies behind the leaf's last word comes along (the array ends in a spare record, capi.hip) and is
+            // whatever lies behind the leaf's last word comes along (the array ends in a spare record, scene_create.hip) and is
             // never read back
             const uint32_t chunks = (count << 1) + ((count + 3u) >> 2);   // ceil(9 count / 4)
             if (lane < chunks)

@@ -1,4 +1,4 @@
-// scene_access_internal.h -- what libshray_query.so (query/) reads of a scene that capi.hip created: the device views the
+// scene_access_internal.h -- what libshray_query.so (query/) reads of a scene that scene_create.hip created: the device views the
 // kernels take, and the FrameView a render would build; what libshray_refit.so (refit/) rewrites in place; and the slots where
 // libshray_point.so (point/), libshray_sdf.so (sdf/) and libshray_winding.so (winding/) keep what they learn of a scene.  Host-only,
 // internal to the libraries; not part of the C ABI.

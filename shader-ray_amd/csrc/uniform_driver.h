@@ -32,7 +32,7 @@ namespace shray {
 // their tallies equal the reference's full traversals (the oracle's); with TIMED_FORM they keep the timed instances'
 // form instead -- sample lanes, shadow rays that stop at their first hit -- and tally what THOSE do
 // (shray_render_counters_timed).
-// ORDERED: the launch reads a dispatch order and its waves report their running times (capi.hip: DispatchOrder) -- an
+// ORDERED: the launch reads a dispatch order and its waves report their running times (dispatch_order.h: DispatchOrder) -- an
 // instance of its own, because the two scalars it carries through the kernel cost the others 2 % (12 B more scratch)
 // unit() of the eye-space ray (x, y, -1): three quotients by one length.  components_in_range (uniform): see the caller; the
 // length itself is checked here (a lane far outside the frame could have an absurd one); the wave takes the true divisions
@@ -151,7 +151,7 @@ __device__ __forceinline__ void trace_pixels_uniform(const SceneView &sc, const 
             // waves leave at once (the caller's test of `slot`).
             const unsigned int log_waves = 2u + log_gx + log_gy;
             const unsigned int k = b >> 3, slot = ((k >> log_waves) << 3) + (b & 7u), wave = k & ((1u << log_waves) - 1u);
-            // heaviest patches first (capi.hip: DispatchOrder): which patch this slot of the launch renders
+            // heaviest patches first (dispatch_order.h: DispatchOrder): which patch this slot of the launch renders
             lp.patch = slot;
             if (ORDERED)
                 lp.patch = fr.dispatch_order ? fr.dispatch_order[slot] : slot;
@@ -192,13 +192,13 @@ __device__ __forceinline__ void trace_pixels_uniform(const SceneView &sc, const 
     // magnitude in [2^-25, 2^25) -- a pixel index plus an offset in (0, 1] --, the divisors shared by the whole launch
     const SharedDivisor by_width = shared_divisor(fw), by_height = shared_divisor(fh);
     const bool eye_in_range = eye_ray_in_range(fr);
-    // The scene's view cache (capi.hip: ViewCache): the timed one-sample instances of the one-wave form read a cached frame's
+    // The scene's view cache (view_cache.h): the timed one-sample instances of the one-wave form read a cached frame's
     // primary directions instead of making them, and a wave whose 64 primary rays all leave the scene stores the cached
     // background pixels instead of looking the environment up.  The two pointers are read from `fr` where they are used, never
     // carried through a traversal.  The background case is a flag and a second arm of the store, NOT an early exit: with a
     // `return` behind the first traversal the register allocator gave the dense instance 60 bytes of scratch instead of 16
     // (R9.1); as written it has 12.
-    // (Not the ORDERED instances: they run one-frame launches and tile sets, which never get the tables -- capi.hip -- and a lone
+    // (Not the ORDERED instances: they run one-frame launches and tile sets, which never get the tables -- view_cache.hip -- and a lone
     // frame was 0.6 % slower for the two tests of the pointers alone.)
     constexpr bool VIEW_RAYS = SHRAY_VIEW_CACHE_RAYS && !COUNT && !ORDERED && ONE_SAMPLE && Traversal::block_size == 64;
     constexpr bool VIEW_SKY = SHRAY_VIEW_CACHE_SKY && !COUNT && !ORDERED && ONE_SAMPLE && Traversal::block_size == 64;

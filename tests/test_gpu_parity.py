@@ -263,7 +263,7 @@ def test_counters_of_the_timed_instances(pkg, gpu, oracle_mod, bunny, env_sky, s
     for material in (0, 6):
         params = world.frame_params(W, H, material=material)
         want, cpu = oracle_mod.render(desc, env_sky, params, W, H, spp)
-        for frames_per_launch in (1, 2):           # the dealt and the plain leaf stage (capi.hip: leaf_stage_policy)
+        for frames_per_launch in (1, 2):           # the dealt and the plain leaf stage (render_api.hip: leaf_stage_policy)
             got, timed = scene.render_counters_timed(params, W, H, spp, frames_per_launch)
             assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (material, spp, frames_per_launch)
             if material == 0:
@@ -397,7 +397,7 @@ def test_dispatch_order_leaves_the_frames_alone(pkg, gpu, bunny):
         pkg.host.trackball_motion(view.object_rotation, 0.05, 0.02)
         frames.append(world.frame_params(W, H, view, material=0))
     streams = [torch.cuda.current_stream(), torch.cuda.Stream()]
-    # the library re-orders launches of one frame and launches of a tile set (capi.hip: launch_stack_views)
+    # the library re-orders launches of one frame and launches of a tile set (render_api.hip: launch_stack_views, dispatch_order.hip)
     for tiles in (None, N.TileSet(32, 32, 3, 1, 2)):
         nbytes = pkg.tracer.tile_buffer_bytes(W, H, tiles)
 
@@ -493,7 +493,7 @@ def test_full_size_properties_1080p(pkg, gpu, oracle_mod, bunny, env_sky):
     for frames_per_launch in (1, 2):
         t_img, t_counters = scene.render_counters_timed(params, W, H, 1, frames_per_launch)
         assert np.array_equal(t_img, a) and t_counters == ca
-    # the stack kernel's two gold instances (capi.hip: leaf_stage_policy): one frame per launch runs the dealt
+    # the stack kernel's two gold instances (render_api.hip: leaf_stage_policy): one frame per launch runs the dealt
     # leaf stage, two frames per launch the plain leaf loop -- the same frame either way, on two streams at once
     import torch
     pair = torch.empty(2, H * W * 4, dtype=torch.float32, device="cuda:0")
