@@ -30,6 +30,7 @@ INSTANCE_OVERLAP_LIB = os.path.join(PKG_DIR, "libshray_instance_overlap.so")
 INTERSECT_LIB = os.path.join(PKG_DIR, "libshray_intersect.so")
 INSTANCE_INTERSECT_LIB = os.path.join(PKG_DIR, "libshray_instance_intersect.so")
 INSTANCE_SDF_LIB = os.path.join(PKG_DIR, "libshray_instance_sdf.so")
+INSTANCE_WINDING_LIB = os.path.join(PKG_DIR, "libshray_instance_winding.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
 HIP_LIB = os.environ.get("SHRAY_HIP_LIB") or os.path.join(PKG_DIR, "libshray_hip.so")
 
@@ -531,6 +532,18 @@ INSTANCE_SDF_SYMBOLS = [
                                                            C.POINTER(Counters)]),
 ]
 
+# include/shader_ray_instance_winding.h --------------------------------------------------------------------
+INSTANCE_WINDING_SYMBOLS = [
+    ("shray_winding_number_instances_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p]),
+    ("shray_winding_number_instances", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
+    ("shray_winding_signed_distance_instances_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p,
+                                                                 C.c_void_p, C.c_void_p]),
+    ("shray_winding_signed_distance_instances", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p]),
+    ("shray_instance_set_orientations", C.c_int, [C.c_void_p, C.c_void_p]),
+]
+
 _host = None
 _hip = None
 _clients = {}   # path -> the loaded client library of libshray_hip.so
@@ -668,6 +681,12 @@ def load_instance_sdf():
     """Loads the instanced signed-distance library (libshray_instance_sdf.so: depends on libshray_instance.so,
     libshray_instance_point.so and libshray_sdf.so too)."""
     return _load_client(INSTANCE_SDF_LIB, INSTANCE_SDF_SYMBOLS)
+
+
+def load_instance_winding():
+    """Loads the instanced winding-number library (libshray_instance_winding.so: depends on libshray_instance.so,
+    libshray_instance_point.so and libshray_winding.so too)."""
+    return _load_client(INSTANCE_WINDING_LIB, INSTANCE_WINDING_SYMBOLS)
 
 
 def check_dist(code: int):

@@ -1331,6 +1331,84 @@ class InstanceSet:
         """Whether every member scene is closed (Scene.surface_info()["closed"]): what the sign's guarantee asks of them."""
         return all(bool(s.surface_info()["closed"]) for s in {id(s): s for s in self._scenes}.values())
 
+    def winding_number(self, points, beta: float = 2.0, containing: bool = False):
+        """Instanced winding numbers (include/shader_ray_instance_winding.h): per world-space point the sum over every instance
+        of the member scene's winding number at the point mapped to object space, negated for a mirroring map: about 1 inside
+        one closed outward-wound instance, 2 where two overlap, 0 outside all; NaN for a point with a non-finite coordinate.
+        `points` and `beta` as for Scene.winding_number.  Host points take the blocking path and return float32 [n]; a GPU
+        tensor on the set's device takes the device path on the current torch stream and returns a float32 [n] tensor.  With
+        containing=True returns (values, int32 [n]): the lowest instance whose own term is above 0.5, or -1."""
+        lib = N.load_instance_winding()
+        points = _host_if_cpu(points)
+        if _is_torch(points):
+            import torch
+            pts = self._device_points(points)
+            out = torch.empty(len(pts), dtype=torch.float32, device=pts.device)
+            inside = torch.empty(len(pts), dtype=torch.int32, device=pts.device) if containing else None
+            stream = torch.cuda.current_stream(pts.device)
+            N.check(lib.shray_winding_number_instances_device(
+                self._handle, C.c_void_p(pts.data_ptr()), len(pts), beta, C.c_void_p(out.data_ptr()),
+                C.c_void_p(inside.data_ptr() if containing else None), C.c_void_p(stream.cuda_stream)))
+            return (out, inside) if containing else out
+        pts = _host_points(points)
+        out = np.empty(len(pts), np.float32)
+        inside = np.empty(len(pts), np.int32) if containing else None
+        N.check(lib.shray_winding_number_instances(self._handle, pts.ctypes.data_as(C.c_void_p), len(pts), beta, out.ctypes.data_as(C.c_void_p),
+                                                   inside.ctypes.data_as(C.c_void_p) if containing else None))
+        return (out, inside) if containing else out
+
+    def winding_number_into(self, points_ptr: int, count: int, out_ptr: int, containing_ptr: int = 0, beta: float = 2.0,
+                            stream_ptr: int = 0):
+        """Asynchronous instanced winding numbers on device memory of the set's device (shray_winding_number_instances_device):
+        `count` shray_point records at `points_ptr` -> `count` float32 at `out_ptr` and, unless `containing_ptr` is 0, int32
+        containing instances there, on a HIP stream (`stream_ptr`)."""
+        N.check(N.load_instance_winding().shray_winding_number_instances_device(
+            self._handle, C.c_void_p(points_ptr), count, beta, C.c_void_p(out_ptr), C.c_void_p(containing_ptr or None), C.c_void_p(stream_ptr)))
+
+    def winding_signed_distance(self, points, max_dist2=None, beta: float = 2.0, closest: bool = False):
+        """Instanced signed distances whose sign comes from the summed winding number
+        (shray_winding_signed_distance_instances): closest_points' record, negative where winding_number is above 0.5, the
+        union's sign; NaN for a point with nothing within its radius.  Arguments and results as for signed_distance."""
+        lib = N.load_instance_winding()
+        points = _host_if_cpu(points)
+        if _is_torch(points):
+            import torch
+            if points.device.index != self.device:
+                raise ValueError(f"points are on {points.device}, the set on cuda:{self.device}")
+            pts = self._scenes[0]._device_points(points, max_dist2)
+            out = torch.empty(len(pts), dtype=torch.float32, device=pts.device)
+            rec = torch.empty((len(pts), 8), dtype=torch.int32, device=pts.device) if closest else None
+            inst = torch.empty(len(pts), dtype=torch.int32, device=pts.device) if closest else None
+            stream = torch.cuda.current_stream(pts.device)
+            N.check(lib.shray_winding_signed_distance_instances_device(
+                self._handle, C.c_void_p(pts.data_ptr()), len(pts), beta, C.c_void_p(out.data_ptr()),
+                C.c_void_p(rec.data_ptr() if closest else None), C.c_void_p(inst.data_ptr() if closest else None),
+                C.c_void_p(stream.cuda_stream)))
+            return (out, rec, inst) if closest else out
+        pts = _host_points(points, max_dist2)
+        out = np.empty(len(pts), np.float32)
+        rec = np.empty(len(pts), CLOSEST_DTYPE) if closest else None
+        inst = np.empty(len(pts), np.int32) if closest else None
+        N.check(lib.shray_winding_signed_distance_instances(
+            self._handle, pts.ctypes.data_as(C.c_void_p), len(pts), beta, out.ctypes.data_as(C.c_void_p),
+            rec.ctypes.data_as(C.c_void_p) if closest else None, inst.ctypes.data_as(C.c_void_p) if closest else None))
+        return (out, rec, inst) if closest else out
+
+    def winding_signed_distance_into(self, points_ptr: int, count: int, out_ptr: int, closest_ptr: int = 0, instances_ptr: int = 0,
+                                     beta: float = 2.0, stream_ptr: int = 0):
+        """Asynchronous instanced winding-signed distances on device memory of the set's device
+        (shray_winding_signed_distance_instances_device), as signed_distance_into."""
+        N.check(N.load_instance_winding().shray_winding_signed_distance_instances_device(
+            self._handle, C.c_void_p(points_ptr), count, beta, C.c_void_p(out_ptr), C.c_void_p(closest_ptr or None),
+            C.c_void_p(instances_ptr or None), C.c_void_p(stream_ptr)))
+
+    def orientations(self) -> np.ndarray:
+        """The orientation of every instance's world-to-object map, float32 [n] of +1 or -1 (-1: a mirror), computed on the
+        device as the winding queries compute it (shray_instance_set_orientations)."""
+        out = np.zeros(self.count, np.float32)
+        N.check(N.load_instance_winding().shray_instance_set_orientations(self._handle, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def triangles_within(self, points, max_near: int = 8, counts: bool = True, counters: bool = False):
         """Instanced within-radius queries (include/shader_ray_instance_near.h): per world-space point the number of
         (instance, triangle) pairs whose closest point lies within its max_dist2, measured on the instances' triangles mapped

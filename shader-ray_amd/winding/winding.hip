@@ -11,7 +11,8 @@
 //
 // A query is one lane per point in one-wave workgroups.  The walk's stack holds node names in LDS, level-major, one level per
 // edge of the tree's height.  A node costs one 16-byte load of { P, r } for the far-field test; a far node then loads N and M,
-// a near branch its child words from copy 7, a near leaf its triangles' corners from the scene's positions.  The winding-signed
+// a near branch its child words from copy 7, a near leaf its triangles' corners from the scene's positions (the walk and its
+// terms are winding/winding_walk.h's, which libshray_instance_winding.so compiles too).  The winding-signed
 // distance runs the closest-point walk (point/point_walk.h, the kernel libshray_point.so runs) and then one lane per point that
 // walks for w where the record is a hit.  This library is built apart from libshray_hip.so, so the renderer's code objects do
 // not change.
@@ -25,6 +26,7 @@
 #include "point_walk.h"
 #include "shader_ray_winding.h"
 #include "trace_common.h"
+#include "winding_walk.h"
 
 using namespace shray;
 
@@ -34,15 +36,11 @@ constexpr int kDeriveBlock = 256;
 constexpr int kTailBlock = 1024;          // heights with at most this many branches run in the one-workgroup launch
 constexpr uint64_t kChunk = 1ull << 22;   // points per scratch chunk when the caller keeps no records
 constexpr int kF = SHRAY_WINDING_DATA_FLOATS;
-constexpr float kInv4Pi = (float)(1.0 / (4.0 * 3.14159265358979323846));
-constexpr float kInv2Pi = (float)(1.0 / (2.0 * 3.14159265358979323846));
 
 // one node's record as the derivation builds it
 struct Moments {
     float P[3], r, N[3], A, M[9];
 };
-
-__device__ __forceinline__ V3 corner(const float *c9, int j) { return mk(c9[3 * j], c9[3 * j + 1], c9[3 * j + 2]); }
 
 // the header's per-triangle terms: N_t, A_t, x_t
 __device__ __forceinline__ void triangle_terms(const float *c9, V3 *nt, float *at, V3 *xt)
@@ -196,70 +194,6 @@ __global__ void __launch_bounds__(kTailBlock) wn_branches_tail(const uint32_t *_
             branch_record(order[i], topo, copy7, data);
         __syncthreads();
     }
-}
-
-// the far-field term of a node whose { P, r } gave d and d2
-__device__ __forceinline__ float far_term(const float4 *__restrict__ rec, V3 d, float d2)
-{
-    const float4 w1 = rec[1], w2 = rec[2], w3 = rec[3], w4 = rec[4];
-    const float len = sqrtf(d2);
-    const float i3 = 1.0f / (d2 * len);
-    const float i5 = i3 / d2;
-    const float tr = (w2.x + w3.x) + w4.x;   // M_00 + M_11 + M_22
-    const V3 m = mk((w2.x * d.x + w2.y * d.y) + w2.z * d.z, (w2.w * d.x + w3.x * d.y) + w3.y * d.z, (w3.z * d.x + w3.w * d.y) + w4.x * d.z);
-    return (((dot3(mk(w1.x, w1.y, w1.z), d) + tr) * i3) - ((3.0f * dot3(d, m)) * i5)) * kInv4Pi;
-}
-
-// the exact term of triangle t (its signed solid angle over 4 pi)
-__device__ __forceinline__ float triangle_term(const float *c9, V3 q)
-{
-    const V3 a = corner(c9, 0) - q, b = corner(c9, 1) - q, c = corner(c9, 2) - q;
-    const float det = dot3(a, cross3(b, c));
-    const float la = sqrtf(dot3(a, a)), lb = sqrtf(dot3(b, b)), lc = sqrtf(dot3(c, c));
-    const float den = (((la * lb) * lc + dot3(a, b) * lc) + dot3(a, c) * lb) + dot3(b, c) * la;
-    return det == 0.0f ? 0.0f : atan_yx(det, den) * kInv2Pi;
-}
-
-struct WindingView {
-    const float4 *records;     // kF floats per node
-    const char *copy7;         // octant copy 7 of the packed tree
-    const float *positions;
-    uint32_t root;             // the root's name
-    float beta;
-};
-
-// w(q; beta) by the walk of the header; `column` is this lane's stack column in LDS (level-major, kBlock apart)
-__device__ __forceinline__ float winding_walk(const WindingView &v, V3 q, uint32_t *column)
-{
-    float w = 0.0f;
-    uint32_t name = v.root;
-    int sp = 0;
-    while (true) {
-        const float4 *rec = v.records + (size_t)5 * (name >> (kNodeShift - kNodeNameShift));
-        const float4 pr = rec[0];
-        const V3 d = mk(pr.x - q.x, pr.y - q.y, pr.z - q.z);
-        const float d2 = dot3(d, d);
-        const float br = v.beta * pr.w;
-        if (d2 > br * br) {
-            w = w + far_term(rec, d, d2);
-        } else {
-            const uint2 ab = *reinterpret_cast<const uint2 *>(v.copy7 + ((size_t)name << kNodeNameShift) + 24);
-            if (!(ab.y & kLeafFlag)) {
-                column[(size_t)sp * kBlock] = ab.y;   // the positive child, after the negative subtree
-                sp++;
-                name = ab.x & kChildNameMask;
-                continue;
-            }
-            const uint32_t end = ab.x + (ab.y & ~kLeafFlag);
-            for (uint32_t t = ab.x; t < end; t++)
-                w = w + triangle_term(v.positions + 9ull * t, q);
-        }
-        if (sp == 0)
-            break;
-        sp--;
-        name = column[(size_t)sp * kBlock];
-    }
-    return w;
 }
 
 struct PointRange {
@@ -515,6 +449,23 @@ int shray_scene_winding_data_download(shray_scene *scene, float *out)
         return rc;
     HIP_TRY(hipEventSynchronize(st->done));   // the derivation may have run on any stream
     HIP_TRY(hipMemcpy(out, st->data.p, st->data.bytes, hipMemcpyDeviceToHost));
+    return SHRAY_OK;
+}
+
+// Outside the header: for libshray_instance_winding.so.  The scene's node records on its device, current for work enqueued
+// on `hip_stream` after the call: prepare()'s one blocking topology readback on the scene's first use, the derivation on that
+// stream when the records are stale, and otherwise a wait of that stream for the derivation's event.  Host-only.
+int shrayi_scene_winding_records(shray_scene *scene, void *hip_stream, const float **d_records)
+{
+    if (!scene || !d_records)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "scene or d_records is NULL");
+    *d_records = nullptr;
+    ShrayQueryScene q;
+    WindingState *st = nullptr;
+    const int rc = prepare(scene, &q, &st, (hipStream_t)hip_stream);
+    if (rc)
+        return rc;
+    *d_records = st->data.as<const float>();
     return SHRAY_OK;
 }
 
