@@ -29,6 +29,7 @@ OVERLAP_LIB = os.path.join(PKG_DIR, "libshray_overlap.so")
 INSTANCE_OVERLAP_LIB = os.path.join(PKG_DIR, "libshray_instance_overlap.so")
 INTERSECT_LIB = os.path.join(PKG_DIR, "libshray_intersect.so")
 INSTANCE_INTERSECT_LIB = os.path.join(PKG_DIR, "libshray_instance_intersect.so")
+CLEARANCE_LIB = os.path.join(PKG_DIR, "libshray_clearance.so")
 INSTANCE_SDF_LIB = os.path.join(PKG_DIR, "libshray_instance_sdf.so")
 INSTANCE_WINDING_LIB = os.path.join(PKG_DIR, "libshray_instance_winding.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
@@ -469,6 +470,35 @@ INTERSECT_SYMBOLS = [
     ("shray_intersect_self", C.c_int, [C.c_void_p, C.POINTER(IntersectParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
 ]
 
+# include/shader_ray_clearance.h ---------------------------------------------------------------------------
+CLEARANCE_MAX = 64
+CLEARANCE_ANY = 1
+CLEARANCE_SKIP_SHARED = 2
+PAIR_INTERSECTING = 15
+
+
+class PairDistance(C.Structure):
+    """shray_pair_distance: a witness on either triangle, the squared distance, the scene triangle and the feature (48 bytes)."""
+    _fields_ = [("on_query", C.c_float * 3), ("dist2", C.c_float), ("on_scene", C.c_float * 3), ("triangle", C.c_int32),
+                ("feature", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class ClearanceParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_pairs", C.c_int32), ("flags", C.c_uint32), ("max_dist2", C.c_float)]
+
+
+CLEARANCE_SYMBOLS = [
+    ("shray_clearance_params_init", None, [C.POINTER(ClearanceParams)]),
+    ("shray_clearance_triangles_device", C.c_int, [C.c_void_p, C.POINTER(ClearanceParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]),
+    ("shray_clearance_triangles", C.c_int, [C.c_void_p, C.POINTER(ClearanceParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    ("shray_clearance_triangles_counters", C.c_int, [C.c_void_p, C.POINTER(ClearanceParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                     C.POINTER(Counters)]),
+    ("shray_clearance_self_device", C.c_int, [C.c_void_p, C.POINTER(ClearanceParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    ("shray_clearance_self", C.c_int, [C.c_void_p, C.POINTER(ClearanceParams), C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+]
+
 # include/shader_ray_instance_multihit.h -------------------------------------------------------------------
 INSTANCE_MULTIHIT_SYMBOLS = [
     ("shray_trace_instances_all_hits_device", C.c_int, [C.c_void_p, C.POINTER(MultihitParams), C.c_void_p, C.c_int64, C.c_void_p,
@@ -650,6 +680,11 @@ def load_overlap():
 def load_intersect():
     """Loads the triangle-intersection query library (libshray_intersect.so)."""
     return _load_client(INTERSECT_LIB, INTERSECT_SYMBOLS)
+
+
+def load_clearance():
+    """Loads the triangle-distance query library (libshray_clearance.so)."""
+    return _load_client(CLEARANCE_LIB, CLEARANCE_SYMBOLS)
 
 
 def load_instance_multihit():

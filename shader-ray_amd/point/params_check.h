@@ -1,10 +1,11 @@
-// params_check.h -- the params refusals of include/shader_ray_overlap.h and include/shader_ray_intersect.h, each made by the
-// query's library (overlap/overlap.hip, intersect/intersect.hip) and by its instanced form (instance_overlap/,
-// instance_intersect/): the struct itself, then the misuse of the ANY flag, which a library makes at its own place among its
+// params_check.h -- the params refusals of include/shader_ray_overlap.h, include/shader_ray_intersect.h and
+// include/shader_ray_clearance.h, each made by the query's library (overlap/overlap.hip, intersect/intersect.hip,
+// clearance/clearance.hip) and by its instanced form (instance_overlap/, instance_intersect/): the struct itself, then the misuse of the ANY flag, which a library makes at its own place among its
 // refusals.  Host code only.
 #pragma once
 
 #include "client_internal.h"
+#include "shader_ray_clearance.h"
 #include "shader_ray_intersect.h"
 #include "shader_ray_overlap.h"
 
@@ -48,6 +49,27 @@ inline int check_any(const shray_intersect_params *op, const void *counts)
 {
     if ((op->flags & SHRAY_INTERSECT_ANY) && (op->max_triangles != 0 || !counts))
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "SHRAY_INTERSECT_ANY needs max_triangles 0 (it is %d) and counts", op->max_triangles);
+    return SHRAY_OK;
+}
+
+// (max_dist2 is not refused: a NaN or a negative one is a query that is not walked)
+inline int check_params(const shray_clearance_params *op)
+{
+    if (!op)
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "clearance params are NULL");
+    if (op->struct_size != sizeof(shray_clearance_params))
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "shray_clearance_params.struct_size is %u, this library expects %zu", op->struct_size,
+                    sizeof(shray_clearance_params));
+    if (op->max_pairs < 0 || op->max_pairs > SHRAY_CLEARANCE_MAX || (op->flags & ~(uint32_t)(SHRAY_CLEARANCE_ANY | SHRAY_CLEARANCE_SKIP_SHARED)))
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "clearance params out of range (max_pairs %d of 0 .. %d, flags 0x%x)", op->max_pairs,
+                    (int)SHRAY_CLEARANCE_MAX, op->flags);
+    return SHRAY_OK;
+}
+
+inline int check_any(const shray_clearance_params *op, const void *counts)
+{
+    if ((op->flags & SHRAY_CLEARANCE_ANY) && (op->max_pairs != 0 || !counts))
+        return fail(SHRAY_ERR_INVALID_ARGUMENT, "SHRAY_CLEARANCE_ANY needs max_pairs 0 (it is %d) and counts", op->max_pairs);
     return SHRAY_OK;
 }
 

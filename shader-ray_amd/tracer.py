@@ -559,6 +559,101 @@ class Scene:
         theirs = np.asarray(other.geometry()["vertex_positions"], np.float32).reshape(-1, 9)
         return self.intersecting_triangles(theirs, max_triangles=max_triangles, counts=counts, any_only=any_only, skip_shared=skip_shared)
 
+    def triangle_distances(self, triangles, max_dist2: float = float("inf"), max_pairs: int = 1, counts: bool = True, counters: bool = False,
+                           skip_shared: bool = False, any_only: bool = False):
+        """Triangle-distance queries (include/shader_ray_clearance.h): per query triangle the number of scene triangles whose
+        squared distance to it is at most `max_dist2` and the `max_pairs` nearest of them in (dist2, triangle) order as
+        PAIR_DISTANCE_DTYPE records (a witness on either triangle, dist2, the scene triangle and the feature; an
+        interpenetrating pair has dist2 0 and feature PAIR_INTERSECTING), the other slots miss records (triangle -1).
+        `triangles` as for intersecting_triangles: host triangles take the blocking path (shray_clearance_triangles) and return
+        (records: PAIR_DISTANCE_DTYPE [n, max_pairs], counts: int32 [n]); a float32 [n, 9] / [n, 12] GPU tensor on the scene's
+        device takes the device path (shray_clearance_triangles_device) on the current torch stream and returns the records
+        as an int32 [n, max_pairs, 12] tensor (the 48 bytes of each: view it as float32 for the coordinates) and the counts
+        as a tensor.  counts=False returns None for the counts and lets the walk skip what cannot reach the nearest
+        `max_pairs`; max_pairs = 0 returns None for the records.  skip_shared=True sets SHRAY_CLEARANCE_SKIP_SHARED, any_only=True
+        (with max_pairs = 0) SHRAY_CLEARANCE_ANY.  counters=True (host triangles only) also returns the walk's counters."""
+        lib = N.load_clearance()
+        return _first_k(self._handle, (lib.shray_clearance_triangles_device, lib.shray_clearance_triangles,
+                                       lib.shray_clearance_triangles_counters),
+                        clearance_params(max_pairs, max_dist2, any_only, skip_shared), max_pairs, "max_pairs", triangles, "triangles",
+                        self._device_triangles, _host_triangles, PAIR_DISTANCE_DTYPE, (12,), False, counts, counters)
+
+    def triangle_distances_into(self, triangles_ptr: int, count: int, out_ptr: int, counts_ptr: int = 0, max_dist2: float = float("inf"),
+                                max_pairs: int = 1, any_only: bool = False, skip_shared: bool = False, stream_ptr: int = 0):
+        """Asynchronous triangle-distance queries on device memory of the scene's device (shray_clearance_triangles_device):
+        `count` shray_triangle records at `triangles_ptr` -> count * max_pairs shray_pair_distance records at `out_ptr` (0 iff
+        max_pairs is 0) and, unless `counts_ptr` is 0, `count` int32 counts there, on a HIP stream (`stream_ptr`)."""
+        op = clearance_params(max_pairs, max_dist2, any_only, skip_shared)
+        N.check(N.load_clearance().shray_clearance_triangles_device(self._handle, C.byref(op), C.c_void_p(triangles_ptr), count,
+                                                                    C.c_void_p(out_ptr or None), C.c_void_p(counts_ptr or None),
+                                                                    C.c_void_p(stream_ptr)))
+
+    def clearance_counts(self, triangles, max_dist2: float, skip_shared: bool = False):
+        """How many scene triangles lie within `max_dist2` of each query triangle (triangle_distances with max_pairs = 0):
+        int32 [n], numpy for host triangles, a tensor for GPU triangles."""
+        return self.triangle_distances(triangles, max_dist2, max_pairs=0, counts=True, skip_shared=skip_shared)[1]
+
+    def within_tolerance(self, triangles, max_dist2: float, skip_shared: bool = False):
+        """Whether any scene triangle lies within `max_dist2` of each query triangle (SHRAY_CLEARANCE_ANY: the walk stops at
+        the first one): bool [n], numpy for host triangles, a tensor for GPU triangles."""
+        return self.triangle_distances(triangles, max_dist2, max_pairs=0, counts=True, skip_shared=skip_shared, any_only=True)[1] != 0
+
+    def self_clearance(self, max_dist2: float = float("inf"), max_pairs: int = 1, skip_shared: bool = True, first: int = 0,
+                       count: int | None = None, counts: bool = True, any_only: bool = False, device: bool = False):
+        """The scene's own triangles [first, first + count) as the queries (shray_clearance_self; count=None: up to the last
+        one), read from the scene's positions as they are when the query runs: how close the mesh comes to itself.  Returns
+        (records: PAIR_DISTANCE_DTYPE [count, max_pairs], counts: int32 [count]) as numpy arrays from the blocking form, or
+        with device=True as tensors on the scene's device (the records int32 [count, max_pairs, 12]) enqueued on the current
+        torch stream (shray_clearance_self_device).  skip_shared defaults to True here: without it every triangle finds
+        itself and its neighbours at distance 0.  max_pairs = 0 returns None for the records, counts=False None for the
+        counts; any_only as for triangle_distances."""
+        if max_pairs == 0 and not counts:
+            raise ValueError("nothing is asked for: max_pairs is 0 and counts is False")
+        triangles = self.triangle_count()
+        if count is None:
+            count = max(triangles - first, 0)
+        op = clearance_params(max_pairs, max_dist2, any_only, skip_shared)
+        lib = N.load_clearance()
+        rows = count if first >= 0 and 0 <= count <= triangles - first else 0   # (the library refuses any other range)
+        if device:
+            import torch
+            where = torch.device("cuda", self.device_index())
+            out = torch.empty((rows, max_pairs, 12), dtype=torch.int32, device=where) if max_pairs > 0 else None
+            n = torch.empty((rows,), dtype=torch.int32, device=where) if counts else None
+            N.check(lib.shray_clearance_self_device(self._handle, C.byref(op), first, count,
+                                                    C.c_void_p(out.data_ptr() if out is not None else None),
+                                                    C.c_void_p(n.data_ptr() if n is not None else None),
+                                                    C.c_void_p(torch.cuda.current_stream(where).cuda_stream)))
+            return out, n
+        out = np.empty((rows, max_pairs), PAIR_DISTANCE_DTYPE) if max_pairs > 0 else None
+        n = np.empty((rows,), np.int32) if counts else None
+        N.check(lib.shray_clearance_self(self._handle, C.byref(op), first, count,
+                                         out.ctypes.data_as(C.c_void_p) if out is not None else None,
+                                         n.ctypes.data_as(C.c_void_p) if n is not None else None))
+        return out, n
+
+    def self_clearance_into(self, first: int, count: int, out_ptr: int, counts_ptr: int = 0, max_dist2: float = float("inf"),
+                            max_pairs: int = 1, any_only: bool = False, skip_shared: bool = True, stream_ptr: int = 0):
+        """Asynchronous self-proximity queries (shray_clearance_self_device): the scene's triangles [first, first + count) ->
+        count * max_pairs shray_pair_distance records at `out_ptr` (0 iff max_pairs is 0) and, unless `counts_ptr` is 0,
+        `count` int32 counts there, device memory of the scene's device, on a HIP stream (`stream_ptr`)."""
+        op = clearance_params(max_pairs, max_dist2, any_only, skip_shared)
+        N.check(N.load_clearance().shray_clearance_self_device(self._handle, C.byref(op), first, count, C.c_void_p(out_ptr or None),
+                                                               C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+
+    def distance_to(self, other: "Scene", max_dist2: float = float("inf"), max_pairs: int = 1, counts: bool = True,
+                    skip_shared: bool = False):
+        """Mesh against mesh: the queries are the other scene's current triangles (other.geometry(), so after its refits), in
+        its triangle order; the blocking host path of triangle_distances on this scene.  Returns (records, counts, minimum):
+        the per-triangle records and counts of triangle_distances, and the smallest dist2 of any pair within `max_dist2` (0
+        where the meshes interpenetrate, +inf where no pair is that near) -- the clearance of the two meshes, squared."""
+        if max_pairs < 1:
+            raise ValueError("distance_to needs max_pairs >= 1: the minimum is read from each query's first record")
+        theirs = np.asarray(other.geometry()["vertex_positions"], np.float32).reshape(-1, 9)
+        records, n = self.triangle_distances(theirs, max_dist2, max_pairs=max_pairs, counts=counts, skip_shared=skip_shared)
+        found = records[:, 0][records[:, 0]["triangle"] >= 0]
+        return records, n, float(found["dist2"].min()) if len(found) else float("inf")
+
     def surface_voxels(self, origin, cell, dims, device=None):
         """The occupancy grid of the surface: bool [nx, ny, nz], voxel (i, j, k) set iff a triangle touches the box
         lo = origin + (i, j, k) * cell, hi = origin + (i + 1, j + 1, k + 1) * cell.  Each bound is one fp32 multiply and one
@@ -683,7 +778,7 @@ def _device_rays(rays, device_index: int, owner: str):
 
 def _first_k(handle, functions, params, k: int, k_name: str, items, kind: str, on_device, on_host, record_dtype, trailing, second: bool,
              counts: bool, counters: bool):
-    """The counted first-K queries (all-hits rays, their instanced form, within-radius, box-overlap, triangle-intersection): per item a
+    """The counted first-K queries (all-hits rays, their instanced form, within-radius, box-overlap, triangle-intersection, triangle-distance): per item a
     count and its first `k` records.  `functions`: the library's device form, blocking form and blocking form with counters, called with
     (`handle`, `params`, items, n, records[, second], counts, ...).  `items` (`kind`: "rays", "points", "boxes"): a GPU tensor
     takes the device path on the current torch stream, through `on_device` (which refuses another device or layout), anything
@@ -835,6 +930,21 @@ def _set_intersect_params(max_triangles: int = 8, any_only: bool = False, skip_s
                 (N.INTERSECT_SKIP_OWN_INSTANCE if skip_own else 0))
     op.reserved = 0
     return op
+
+
+def clearance_params(max_pairs: int = 1, max_dist2: float = float("inf"), any_only: bool = False,
+                     skip_shared: bool = False) -> N.ClearanceParams:
+    op = N.ClearanceParams()
+    N.load_clearance().shray_clearance_params_init(C.byref(op))
+    op.max_pairs = max_pairs
+    op.flags = (N.CLEARANCE_ANY if any_only else 0) | (N.CLEARANCE_SKIP_SHARED if skip_shared else 0)
+    op.max_dist2 = float(max_dist2)   # (ctypes rounds a python float to float32)
+    return op
+
+
+# a record of the triangle-distance query (include/shader_ray_clearance.h): 48 bytes per element
+PAIR_DISTANCE_DTYPE = np.dtype([("on_query", np.float32, 3), ("dist2", np.float32), ("on_scene", np.float32, 3), ("triangle", np.int32),
+                                ("feature", np.int32), ("reserved", np.int32, 3)])
 
 
 # a triangle buffer of the triangle-intersection query (include/shader_ray_intersect.h): 48 bytes per element
