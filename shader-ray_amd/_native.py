@@ -30,6 +30,7 @@ INSTANCE_OVERLAP_LIB = os.path.join(PKG_DIR, "libshray_instance_overlap.so")
 INTERSECT_LIB = os.path.join(PKG_DIR, "libshray_intersect.so")
 INSTANCE_INTERSECT_LIB = os.path.join(PKG_DIR, "libshray_instance_intersect.so")
 CLEARANCE_LIB = os.path.join(PKG_DIR, "libshray_clearance.so")
+INSTANCE_CLEARANCE_LIB = os.path.join(PKG_DIR, "libshray_instance_clearance.so")
 INSTANCE_SDF_LIB = os.path.join(PKG_DIR, "libshray_instance_sdf.so")
 INSTANCE_WINDING_LIB = os.path.join(PKG_DIR, "libshray_instance_winding.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
@@ -553,6 +554,22 @@ INSTANCE_INTERSECT_SYMBOLS = [
                                            C.c_void_p, C.c_void_p]),
 ]
 
+# include/shader_ray_instance_clearance.h ------------------------------------------------------------------
+CLEARANCE_SKIP_OWN_INSTANCE = 4   # the instance form only
+
+INSTANCE_CLEARANCE_SYMBOLS = [
+    ("shray_clearance_triangles_instances_device", C.c_int, [C.c_void_p, C.POINTER(ClearanceParams), C.c_void_p, C.c_int64, C.c_void_p,
+                                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("shray_clearance_triangles_instances", C.c_int, [C.c_void_p, C.POINTER(ClearanceParams), C.c_void_p, C.c_int64, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p]),
+    ("shray_clearance_triangles_instances_counters", C.c_int, [C.c_void_p, C.POINTER(ClearanceParams), C.c_void_p, C.c_int64, C.c_void_p,
+                                                               C.c_void_p, C.c_void_p, C.POINTER(Counters)]),
+    ("shray_clearance_instance_device", C.c_int, [C.c_void_p, C.POINTER(ClearanceParams), C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("shray_clearance_instance", C.c_int, [C.c_void_p, C.POINTER(ClearanceParams), C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+]
+
 # include/shader_ray_instance_sdf.h ------------------------------------------------------------------------
 INSTANCE_SDF_SYMBOLS = [
     ("shray_signed_distance_instances_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -710,6 +727,11 @@ def load_instance_overlap():
 def load_instance_intersect():
     """Loads the instanced triangle-intersection library (libshray_instance_intersect.so: depends on libshray_instance.so too)."""
     return _load_client(INSTANCE_INTERSECT_LIB, INSTANCE_INTERSECT_SYMBOLS)
+
+
+def load_instance_clearance():
+    """Loads the instanced triangle-distance library (libshray_instance_clearance.so: depends on libshray_instance.so too)."""
+    return _load_client(INSTANCE_CLEARANCE_LIB, INSTANCE_CLEARANCE_SYMBOLS)
 
 
 def load_instance_sdf():

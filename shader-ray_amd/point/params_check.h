@@ -1,6 +1,6 @@
 // params_check.h -- the params refusals of include/shader_ray_overlap.h, include/shader_ray_intersect.h and
 // include/shader_ray_clearance.h, each made by the query's library (overlap/overlap.hip, intersect/intersect.hip,
-// clearance/clearance.hip) and by its instanced form (instance_overlap/, instance_intersect/): the struct itself, then the misuse of the ANY flag, which a library makes at its own place among its
+// clearance/clearance.hip) and by its instanced form (instance_overlap/, instance_intersect/, instance_clearance/): the struct itself, then the misuse of the ANY flag, which a library makes at its own place among its
 // refusals.  Host code only.
 #pragma once
 
@@ -53,14 +53,15 @@ inline int check_any(const shray_intersect_params *op, const void *counts)
 }
 
 // (max_dist2 is not refused: a NaN or a negative one is a query that is not walked)
-inline int check_params(const shray_clearance_params *op)
+// `known`: the flags of the form that asks (only instance_clearance/'s instance form knows SHRAY_CLEARANCE_SKIP_OWN_INSTANCE)
+inline int check_params(const shray_clearance_params *op, uint32_t known = SHRAY_CLEARANCE_ANY | SHRAY_CLEARANCE_SKIP_SHARED)
 {
     if (!op)
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "clearance params are NULL");
     if (op->struct_size != sizeof(shray_clearance_params))
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "shray_clearance_params.struct_size is %u, this library expects %zu", op->struct_size,
                     sizeof(shray_clearance_params));
-    if (op->max_pairs < 0 || op->max_pairs > SHRAY_CLEARANCE_MAX || (op->flags & ~(uint32_t)(SHRAY_CLEARANCE_ANY | SHRAY_CLEARANCE_SKIP_SHARED)))
+    if (op->max_pairs < 0 || op->max_pairs > SHRAY_CLEARANCE_MAX || (op->flags & ~known))
         return fail(SHRAY_ERR_INVALID_ARGUMENT, "clearance params out of range (max_pairs %d of 0 .. %d, flags 0x%x)", op->max_pairs,
                     (int)SHRAY_CLEARANCE_MAX, op->flags);
     return SHRAY_OK;

@@ -942,6 +942,19 @@ def clearance_params(max_pairs: int = 1, max_dist2: float = float("inf"), any_on
     return op
 
 
+def _set_clearance_params(max_pairs: int = 1, max_dist2: float = float("inf"), any_only: bool = False, skip_shared: bool = False,
+                          skip_own: bool = False) -> N.ClearanceParams:
+    """shray_clearance_params for the instanced query, filled here: libshray_instance_clearance.so does not need
+    libshray_clearance.so.  skip_own sets SHRAY_CLEARANCE_SKIP_OWN_INSTANCE, which only the instance form accepts."""
+    op = N.ClearanceParams()
+    op.struct_size = C.sizeof(N.ClearanceParams)
+    op.max_pairs = max_pairs
+    op.flags = ((N.CLEARANCE_ANY if any_only else 0) | (N.CLEARANCE_SKIP_SHARED if skip_shared else 0) |
+                (N.CLEARANCE_SKIP_OWN_INSTANCE if skip_own else 0))
+    op.max_dist2 = float(max_dist2)   # (ctypes rounds a python float to float32)
+    return op
+
+
 # a record of the triangle-distance query (include/shader_ray_clearance.h): 48 bytes per element
 PAIR_DISTANCE_DTYPE = np.dtype([("on_query", np.float32, 3), ("dist2", np.float32), ("on_scene", np.float32, 3), ("triangle", np.int32),
                                 ("feature", np.int32), ("reserved", np.int32, 3)])
@@ -1717,6 +1730,113 @@ class InstanceSet:
         SHRAY_INTERSECT_SKIP_OWN_INSTANCE launch of the instance form per instance)."""
         return np.array([bool(self.instance_intersections(i, max_triangles=0, counts=True, any_only=True)[2].any())
                          for i in range(self.count)], bool)
+
+    def triangle_distances(self, triangles, max_dist2: float = float("inf"), max_pairs: int = 1, counts: bool = True, counters: bool = False,
+                           skip_shared: bool = False, any_only: bool = False):
+        """Instanced triangle-distance queries (include/shader_ray_instance_clearance.h): per world query triangle the number
+        of (instance, triangle) pairs whose squared distance to it is at most `max_dist2`, computed on the instances'
+        triangles mapped to the world by the set's object-to-world floats, and the `max_pairs` nearest of them in (dist2,
+        instance, triangle) order as PAIR_DISTANCE_DTYPE records (world witnesses and dist2, the member scene's own triangle
+        index), the other slots miss records (triangle -1) with instance -1.  `triangles` as for Scene.triangle_distances:
+        host triangles take the blocking path and return (records: PAIR_DISTANCE_DTYPE [n, max_pairs], instances: int32 [n,
+        max_pairs], counts: int32 [n]); a float32 [n, 9] / [n, 12] GPU tensor on the set's device takes the device path on the
+        current torch stream and returns the records as an int32 [n, max_pairs, 12] tensor and the others as tensors.
+        counts=False returns None for the counts and lets the walk skip what cannot reach the nearest `max_pairs`; max_pairs
+        = 0 returns None for the records and instances.  skip_shared=True sets SHRAY_CLEARANCE_SKIP_SHARED, judged on world
+        corners; any_only=True (with max_pairs = 0) SHRAY_CLEARANCE_ANY.  counters=True (host triangles only) also returns the
+        counters of the walk that prunes by max_dist2 only, summed over a query's walks."""
+        lib = N.load_instance_clearance()
+        return _first_k(self._handle, (lib.shray_clearance_triangles_instances_device, lib.shray_clearance_triangles_instances,
+                                       lib.shray_clearance_triangles_instances_counters),
+                        _set_clearance_params(max_pairs, max_dist2, any_only, skip_shared), max_pairs, "max_pairs", triangles, "triangles",
+                        self._device_triangles, _host_triangles, PAIR_DISTANCE_DTYPE, (12,), True, counts, counters)
+
+    def triangle_distances_into(self, triangles_ptr: int, count: int, out_ptr: int, instances_ptr: int = 0, counts_ptr: int = 0,
+                                max_dist2: float = float("inf"), max_pairs: int = 1, any_only: bool = False, skip_shared: bool = False,
+                                stream_ptr: int = 0):
+        """Asynchronous instanced triangle-distance queries on device memory of the set's device
+        (shray_clearance_triangles_instances_device): `count` shray_triangle records at `triangles_ptr` -> count * max_pairs
+        shray_pair_distance records at `out_ptr` (0 iff max_pairs is 0), unless `instances_ptr` is 0 count * max_pairs int32
+        instance indices there, and unless `counts_ptr` is 0 `count` int32 counts there, on a HIP stream (`stream_ptr`)."""
+        op = _set_clearance_params(max_pairs, max_dist2, any_only, skip_shared)
+        N.check(N.load_instance_clearance().shray_clearance_triangles_instances_device(
+            self._handle, C.byref(op), C.c_void_p(triangles_ptr), count, C.c_void_p(out_ptr or None), C.c_void_p(instances_ptr or None),
+            C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+
+    def clearance_counts(self, triangles, max_dist2: float, skip_shared: bool = False):
+        """How many (instance, triangle) pairs lie within `max_dist2` of each world query triangle (triangle_distances with
+        max_pairs = 0): int32 [n], numpy for host triangles, a tensor for GPU triangles."""
+        return self.triangle_distances(triangles, max_dist2, max_pairs=0, counts=True, skip_shared=skip_shared)[2]
+
+    def within_tolerance(self, triangles, max_dist2: float, skip_shared: bool = False):
+        """Whether any triangle of any instance lies within `max_dist2` of each world query triangle (SHRAY_CLEARANCE_ANY: a
+        query stops at its first member): bool [n], numpy for host triangles, a tensor for GPU triangles."""
+        return self.triangle_distances(triangles, max_dist2, max_pairs=0, counts=True, skip_shared=skip_shared, any_only=True)[2] != 0
+
+    def instance_clearance(self, instance: int, max_dist2: float = float("inf"), max_pairs: int = 1, skip_shared: bool = False,
+                           skip_own: bool = True, first: int = 0, count: int | None = None, counts: bool = True, any_only: bool = False,
+                           device: bool = False):
+        """The instance form (shray_clearance_instance): the queries are the triangles [first, first + count) of instance
+        `instance`'s scene (count=None: up to the last one) under that instance's current map, read on the device when the
+        query runs.  Returns (records: PAIR_DISTANCE_DTYPE [count, max_pairs], instances: int32 [count, max_pairs], counts:
+        int32 [count]) as numpy arrays from the blocking form, or with device=True as tensors on the set's device (the records
+        int32 [count, max_pairs, 12]) enqueued on the current torch stream (shray_clearance_instance_device).  skip_own
+        defaults to True here (SHRAY_CLEARANCE_SKIP_OWN_INSTANCE): no pair of instance `instance` itself is a member -- by its
+        index, so a duplicate instance at the same place is found at distance 0.  max_pairs = 0 returns None for the records
+        and instances, counts=False None for the counts; any_only and skip_shared as for triangle_distances."""
+        if max_pairs == 0 and not counts:
+            raise ValueError("nothing is asked for: max_pairs is 0 and counts is False")
+        triangles = self.triangle_count(instance) if 0 <= instance < self.count else 0   # (the library refuses another instance)
+        if count is None:
+            count = max(triangles - first, 0)
+        op = _set_clearance_params(max_pairs, max_dist2, any_only, skip_shared, skip_own)
+        lib = N.load_instance_clearance()
+        rows = count if first >= 0 and 0 <= count <= triangles - first else 0   # (the library refuses any other range)
+        if device:
+            import torch
+            where = torch.device("cuda", self.device)
+            # (an empty tensor has no pointer: one row is allocated for an empty range)
+            new = lambda want, *shape: torch.empty((max(rows, 1), *shape), dtype=torch.int32, device=where) if want else None
+            outs = (new(max_pairs > 0, max_pairs, 12), new(max_pairs > 0, max_pairs), new(counts))
+            N.check(lib.shray_clearance_instance_device(self._handle, C.byref(op), instance, first, count,
+                                                        *(C.c_void_p(o.data_ptr() if o is not None else None) for o in outs),
+                                                        C.c_void_p(torch.cuda.current_stream(where).cuda_stream)))
+            return tuple(None if o is None else o[:rows] for o in outs)
+        new = lambda want, dtype, *shape: np.empty((rows, *shape), dtype) if want else None
+        out, inst, n = new(max_pairs > 0, PAIR_DISTANCE_DTYPE, max_pairs), new(max_pairs > 0, np.int32, max_pairs), new(counts, np.int32)
+        N.check(lib.shray_clearance_instance(self._handle, C.byref(op), instance, first, count,
+                                             *(o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (out, inst, n))))
+        return out, inst, n
+
+    def instance_clearance_into(self, instance: int, first: int, count: int, out_ptr: int, instances_ptr: int = 0, counts_ptr: int = 0,
+                                max_dist2: float = float("inf"), max_pairs: int = 1, any_only: bool = False, skip_shared: bool = False,
+                                skip_own: bool = True, stream_ptr: int = 0):
+        """Asynchronous instance form (shray_clearance_instance_device): the triangles [first, first + count) of instance
+        `instance` -> count * max_pairs shray_pair_distance records at `out_ptr` (0 iff max_pairs is 0), unless
+        `instances_ptr` is 0 as many int32 instance indices there, and unless `counts_ptr` is 0 `count` int32 counts there,
+        device memory of the set's device, on a HIP stream (`stream_ptr`)."""
+        op = _set_clearance_params(max_pairs, max_dist2, any_only, skip_shared, skip_own)
+        N.check(N.load_instance_clearance().shray_clearance_instance_device(
+            self._handle, C.byref(op), instance, first, count, C.c_void_p(out_ptr or None), C.c_void_p(instances_ptr or None),
+            C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+
+    def instances_within(self, max_dist2: float) -> np.ndarray:
+        """bool [n]: instance i has a triangle within `max_dist2` of a triangle of another instance (one SHRAY_CLEARANCE_ANY |
+        SHRAY_CLEARANCE_SKIP_OWN_INSTANCE launch of the instance form per instance)."""
+        return np.array([bool(self.instance_clearance(i, max_dist2, max_pairs=0, counts=True, any_only=True)[2].any())
+                         for i in range(self.count)], bool)
+
+    def instance_distance(self, instance: int, max_dist2: float = float("inf"), max_pairs: int = 1, counts: bool = True,
+                          skip_shared: bool = False):
+        """Instance `instance` against the rest of the set: the blocking instance form with SHRAY_CLEARANCE_SKIP_OWN_INSTANCE over
+        all of its triangles.  Returns (records, instances, counts, minimum): instance_clearance's arrays, and the smallest
+        dist2 of any pair within `max_dist2` (0 where the instance interpenetrates another, +inf where no pair is that near)
+        -- the clearance of the instance from the others, squared; reduced on the host as Scene.distance_to does."""
+        if max_pairs < 1:
+            raise ValueError("instance_distance needs max_pairs >= 1: the minimum is read from each query's first record")
+        records, inst, n = self.instance_clearance(instance, max_dist2, max_pairs=max_pairs, skip_shared=skip_shared, counts=counts)
+        found = records[:, 0][records[:, 0]["triangle"] >= 0]
+        return records, inst, n, float(found["dist2"].min()) if len(found) else float("inf")
 
     def close(self):
         if getattr(self, "_handle", None):
