@@ -31,6 +31,7 @@ INTERSECT_LIB = os.path.join(PKG_DIR, "libshray_intersect.so")
 INSTANCE_INTERSECT_LIB = os.path.join(PKG_DIR, "libshray_instance_intersect.so")
 CLEARANCE_LIB = os.path.join(PKG_DIR, "libshray_clearance.so")
 INSTANCE_CLEARANCE_LIB = os.path.join(PKG_DIR, "libshray_instance_clearance.so")
+INSTANCE_PAIRS_LIB = os.path.join(PKG_DIR, "libshray_instance_pairs.so")
 INSTANCE_SDF_LIB = os.path.join(PKG_DIR, "libshray_instance_sdf.so")
 INSTANCE_WINDING_LIB = os.path.join(PKG_DIR, "libshray_instance_winding.so")
 # SHRAY_HIP_LIB selects an experiment build of the same library (profiles/variant_sweep.sh); unset in normal use
@@ -570,6 +571,25 @@ INSTANCE_CLEARANCE_SYMBOLS = [
                                            C.c_void_p, C.c_void_p]),
 ]
 
+# include/shader_ray_instance_pairs.h ----------------------------------------------------------------------
+PAIRS_ANY = 1
+PAIRS_SKIP_SHARED = 2
+PAIRS_UPPER = 4
+PAIRS_NONE = 0xFFFFFFFFFFFFFFFF
+PAIRS_MAX_WORKGROUPS = 1 << 24
+
+
+class PairsParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("first_row", C.c_int32), ("row_count", C.c_int32)]
+
+
+INSTANCE_PAIRS_SYMBOLS = [
+    ("shray_instance_pairs_intersect_device", C.c_int, [C.c_void_p, C.POINTER(PairsParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("shray_instance_pairs_intersect", C.c_int, [C.c_void_p, C.POINTER(PairsParams), C.c_void_p, C.c_void_p]),
+    ("shray_instance_pairs_intersect_counters", C.c_int, [C.c_void_p, C.POINTER(PairsParams), C.c_void_p, C.c_void_p,
+                                                          C.POINTER(Counters)]),
+]
+
 # include/shader_ray_instance_sdf.h ------------------------------------------------------------------------
 INSTANCE_SDF_SYMBOLS = [
     ("shray_signed_distance_instances_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -732,6 +752,11 @@ def load_instance_intersect():
 def load_instance_clearance():
     """Loads the instanced triangle-distance library (libshray_instance_clearance.so: depends on libshray_instance.so too)."""
     return _load_client(INSTANCE_CLEARANCE_LIB, INSTANCE_CLEARANCE_SYMBOLS)
+
+
+def load_instance_pairs():
+    """Loads the instance-pair collision-matrix library (libshray_instance_pairs.so: depends on libshray_instance.so too)."""
+    return _load_client(INSTANCE_PAIRS_LIB, INSTANCE_PAIRS_SYMBOLS)
 
 
 def load_instance_sdf():

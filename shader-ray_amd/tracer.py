@@ -932,6 +932,16 @@ def _set_intersect_params(max_triangles: int = 8, any_only: bool = False, skip_s
     return op
 
 
+def _pairs_params(first_row: int = 0, row_count: int = 0, any_only: bool = False, upper: bool = False,
+                  skip_shared: bool = False) -> N.PairsParams:
+    """shray_pairs_params (include/shader_ray_instance_pairs.h)"""
+    op = N.PairsParams()
+    op.struct_size = C.sizeof(N.PairsParams)
+    op.flags = (N.PAIRS_ANY if any_only else 0) | (N.PAIRS_SKIP_SHARED if skip_shared else 0) | (N.PAIRS_UPPER if upper else 0)
+    op.first_row, op.row_count = first_row, row_count
+    return op
+
+
 def clearance_params(max_pairs: int = 1, max_dist2: float = float("inf"), any_only: bool = False,
                      skip_shared: bool = False) -> N.ClearanceParams:
     op = N.ClearanceParams()
@@ -1730,6 +1740,83 @@ class InstanceSet:
         SHRAY_INTERSECT_SKIP_OWN_INSTANCE launch of the instance form per instance)."""
         return np.array([bool(self.instance_intersections(i, max_triangles=0, counts=True, any_only=True)[2].any())
                          for i in range(self.count)], bool)
+
+    def _pair_rows(self, rows):
+        """(first_row, row_count) of `rows`: None (every instance), a (first_row, row_count) pair, or a range of step 1"""
+        if rows is None:
+            return 0, self.count
+        if isinstance(rows, range):
+            if rows.step != 1:
+                raise ValueError("rows must be a range of step 1")
+            return rows.start, len(rows)
+        first_row, row_count = rows
+        return int(first_row), int(row_count)
+
+    def collision_matrix(self, rows=None, upper: bool = False, skip_shared: bool = False) -> np.ndarray:
+        """Which placed parts collide, and with which other part (include/shader_ray_instance_pairs.h, SHRAY_PAIRS_ANY): bool
+        [r, n], entry (a - first_row, b) set iff a triangle of instance a, as the query, intersects a triangle of instance b;
+        one launch for all the rows.  `rows`: None for every instance, else (first_row, row_count) or a range.  The matrix is
+        ordered (the per-pair test is not symmetric in fp32) and its diagonal is False; upper=True asks for the cells with b >
+        a only, skip_shared=True sets SHRAY_PAIRS_SKIP_SHARED."""
+        first_row, row_count = self._pair_rows(rows)
+        ok = first_row >= 0 and row_count >= 0 and first_row + row_count <= self.count   # (the library refuses any other range)
+        cells = np.empty((row_count if ok else 0, self.count), np.int64)
+        op = _pairs_params(first_row, row_count, True, upper, skip_shared)
+        N.check(N.load_instance_pairs().shray_instance_pairs_intersect(self._handle, C.byref(op), None, cells.ctypes.data_as(C.c_void_p)))
+        return cells != 0
+
+    def collision_pairs(self, rows=None, counts: bool = True, upper: bool = False, skip_shared: bool = False, counters: bool = False,
+                        device: bool = False):
+        """The collision matrix with its witnesses (include/shader_ray_instance_pairs.h): (triangle_a: int32 [r, n],
+        triangle_b: int32 [r, n], counts: int64 [r, n]).  Cell (a - first_row, b) holds the number of pairs (triangle ta of
+        instance a as the query, triangle tb of instance b) that intersect, and the lexicographically smallest such (ta, tb),
+        -1 and -1 where there is none.  counts=False returns None for the counts and lets the walk skip what cannot lower a
+        cell's pair.  Numpy arrays from the blocking form, or with device=True tensors on the set's device enqueued on the
+        current torch stream.  counters=True (the blocking form only) also returns the counters of the walk that skips
+        nothing by what a cell already holds.  `rows`, upper and skip_shared as for collision_matrix."""
+        first_row, row_count = self._pair_rows(rows)
+        ok = first_row >= 0 and row_count >= 0 and first_row + row_count <= self.count   # (the library refuses any other range)
+        r, n = (row_count if ok else 0), self.count
+        op = _pairs_params(first_row, row_count, False, upper, skip_shared)
+        lib = N.load_instance_pairs()
+        if device:
+            import torch
+            if counters:
+                raise ValueError("counters are counted on the host path: pass device=False")
+            where = torch.device("cuda", self.device)
+            # (an empty tensor has no pointer: one cell is allocated for an empty range)
+            new = lambda want: torch.empty(max(r * n, 1), dtype=torch.int64, device=where) if want else None
+            keys, cnt = new(True), new(counts)
+            N.check(lib.shray_instance_pairs_intersect_device(self._handle, C.byref(op), C.c_void_p(keys.data_ptr()),
+                                                              C.c_void_p(cnt.data_ptr() if counts else None),
+                                                              C.c_void_p(torch.cuda.current_stream(where).cuda_stream)))
+            keys = keys[:r * n].reshape(r, n)       # (SHRAY_PAIRS_NONE is -1 as an int64: both halves come out -1)
+            return (keys >> 32).to(torch.int32), (keys & 0xFFFFFFFF).to(torch.int32), (cnt[:r * n].reshape(r, n) if counts else None)
+        keys = np.empty((r, n), np.uint64)
+        cnt = np.empty((r, n), np.int64) if counts else None
+        args = (self._handle, C.byref(op), keys.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p) if counts else None)
+        tally = N.Counters()
+        N.check(lib.shray_instance_pairs_intersect_counters(*args, C.byref(tally)) if counters else lib.shray_instance_pairs_intersect(*args))
+        out = ((keys >> np.uint64(32)).astype(np.uint32).view(np.int32), (keys & np.uint64(0xFFFFFFFF)).astype(np.uint32).view(np.int32), cnt)
+        return (*out, tally.as_dict()) if counters else out
+
+    def collision_pairs_into(self, first_ptr: int, counts_ptr: int, first_row: int = 0, row_count: int | None = None,
+                             any_only: bool = False, upper: bool = False, skip_shared: bool = False, stream_ptr: int = 0):
+        """Asynchronous collision matrix on device memory of the set's device (shray_instance_pairs_intersect_device): the
+        rows [first_row, first_row + row_count) (row_count=None: up to the last instance) -> row_count * n uint64 keys (ta <<
+        32 | tb, all ones where none) at `first_ptr` unless it is 0, and row_count * n int64 counts at `counts_ptr` unless it is
+        0, on a HIP stream (`stream_ptr`).  The call initialises the cells itself.  any_only=True (with first_ptr 0) writes 1
+        or 0 into the counts."""
+        if row_count is None:
+            row_count = max(self.count - first_row, 0)
+        op = _pairs_params(first_row, row_count, any_only, upper, skip_shared)
+        N.check(N.load_instance_pairs().shray_instance_pairs_intersect_device(
+            self._handle, C.byref(op), C.c_void_p(first_ptr or None), C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+
+    def colliding_pairs(self, upper: bool = True) -> np.ndarray:
+        """int32 [m, 2]: the set cells (a, b) of collision_matrix in row-major order; with upper=True (the default) every
+        unordered pair is asked once, as (a, b) with a < b and instance a's triangles as the queries."""
+        return np.argwhere(self.collision_matrix(upper=upper)).astype(np.int32).reshape(-1, 2)
 
     def triangle_distances(self, triangles, max_dist2: float = float("inf"), max_pairs: int = 1, counts: bool = True, counters: bool = False,
                            skip_shared: bool = False, any_only: bool = False):
