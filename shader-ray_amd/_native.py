@@ -663,112 +663,54 @@ def _load_client(path, symbols):
     return _clients[path]
 
 
-def load_dist():
-    """Loads the multi-GPU frame loop (libshray_dist.so: depends on libshray_hip.so and RCCL; torch bundles both)."""
-    return _load_client(DIST_LIB, DIST_SYMBOLS)
+# The client libraries of libshray_hip.so in the order load_all loads them: (name, path, symbols, what it is).  Each has a loader
+# of its own, load_<name>(); all but the first report their errors through shray_last_error.  The instanced ones depend on
+# libshray_instance.so too, the instanced signed-distance and winding-number ones also on libshray_instance_point.so and on
+# libshray_sdf.so / libshray_winding.so.
+CLIENT_LIBRARIES = (
+    ("dist", DIST_LIB, DIST_SYMBOLS, "the multi-GPU frame loop (depends on RCCL too; torch bundles it)"),
+    ("query", QUERY_LIB, QUERY_SYMBOLS, "the ray-query library"),
+    ("refit", REFIT_LIB, REFIT_SYMBOLS, "the refit library"),
+    ("instance", INSTANCE_LIB, INSTANCE_SYMBOLS + INSTANCE_INTERNAL_SYMBOLS, "the instanced-query library, with its test accessor"),
+    ("point", POINT_LIB, POINT_SYMBOLS, "the closest-point library"),
+    ("sdf", SDF_LIB, SDF_SYMBOLS, "the signed-distance library"),
+    ("winding", WINDING_LIB, WINDING_SYMBOLS, "the winding-number library"),
+    ("multihit", MULTIHIT_LIB, MULTIHIT_SYMBOLS, "the all-hits ray-query library"),
+    ("near", NEAR_LIB, NEAR_SYMBOLS, "the within-radius query library"),
+    ("overlap", OVERLAP_LIB, OVERLAP_SYMBOLS, "the box-overlap query library"),
+    ("intersect", INTERSECT_LIB, INTERSECT_SYMBOLS, "the triangle-intersection query library"),
+    ("clearance", CLEARANCE_LIB, CLEARANCE_SYMBOLS, "the triangle-distance query library"),
+    ("instance_multihit", INSTANCE_MULTIHIT_LIB, INSTANCE_MULTIHIT_SYMBOLS, "the instanced all-hits library"),
+    ("instance_point", INSTANCE_POINT_LIB, INSTANCE_POINT_SYMBOLS, "the instanced closest-point library"),
+    ("instance_near", INSTANCE_NEAR_LIB, INSTANCE_NEAR_SYMBOLS, "the instanced within-radius library"),
+    ("instance_overlap", INSTANCE_OVERLAP_LIB, INSTANCE_OVERLAP_SYMBOLS, "the instanced box-overlap library"),
+    ("instance_intersect", INSTANCE_INTERSECT_LIB, INSTANCE_INTERSECT_SYMBOLS, "the instanced triangle-intersection library"),
+    ("instance_clearance", INSTANCE_CLEARANCE_LIB, INSTANCE_CLEARANCE_SYMBOLS, "the instanced triangle-distance library"),
+    ("instance_pairs", INSTANCE_PAIRS_LIB, INSTANCE_PAIRS_SYMBOLS, "the instance-pair collision-matrix library"),
+    ("instance_sdf", INSTANCE_SDF_LIB, INSTANCE_SDF_SYMBOLS, "the instanced signed-distance library"),
+    ("instance_winding", INSTANCE_WINDING_LIB, INSTANCE_WINDING_SYMBOLS, "the instanced winding-number library"),
+)
 
 
-# the client libraries below report their errors through shray_last_error
-def load_query():
-    """Loads the ray-query library (libshray_query.so)."""
-    return _load_client(QUERY_LIB, QUERY_SYMBOLS)
+def _loader(name, path, symbols, what):
+    def load():
+        return _load_client(path, symbols)
+    load.__name__ = load.__qualname__ = f"load_{name}"
+    load.__doc__ = f"Loads {what} ({os.path.basename(path)})."
+    return load
 
 
-def load_refit():
-    """Loads the refit library (libshray_refit.so)."""
-    return _load_client(REFIT_LIB, REFIT_SYMBOLS)
+for _entry in CLIENT_LIBRARIES:   # load_dist(), load_query(), ..., load_instance_winding()
+    globals()[f"load_{_entry[0]}"] = _loader(*_entry)
+del _entry
 
 
-def load_instance():
-    """Loads the instanced-query library (libshray_instance.so), with its test accessor."""
-    return _load_client(INSTANCE_LIB, INSTANCE_SYMBOLS + INSTANCE_INTERNAL_SYMBOLS)
-
-
-def load_point():
-    """Loads the closest-point library (libshray_point.so)."""
-    return _load_client(POINT_LIB, POINT_SYMBOLS)
-
-
-def load_sdf():
-    """Loads the signed-distance library (libshray_sdf.so)."""
-    return _load_client(SDF_LIB, SDF_SYMBOLS)
-
-
-def load_winding():
-    """Loads the winding-number library (libshray_winding.so)."""
-    return _load_client(WINDING_LIB, WINDING_SYMBOLS)
-
-
-def load_multihit():
-    """Loads the all-hits ray-query library (libshray_multihit.so)."""
-    return _load_client(MULTIHIT_LIB, MULTIHIT_SYMBOLS)
-
-
-def load_near():
-    """Loads the within-radius query library (libshray_near.so)."""
-    return _load_client(NEAR_LIB, NEAR_SYMBOLS)
-
-
-def load_overlap():
-    """Loads the box-overlap query library (libshray_overlap.so)."""
-    return _load_client(OVERLAP_LIB, OVERLAP_SYMBOLS)
-
-
-def load_intersect():
-    """Loads the triangle-intersection query library (libshray_intersect.so)."""
-    return _load_client(INTERSECT_LIB, INTERSECT_SYMBOLS)
-
-
-def load_clearance():
-    """Loads the triangle-distance query library (libshray_clearance.so)."""
-    return _load_client(CLEARANCE_LIB, CLEARANCE_SYMBOLS)
-
-
-def load_instance_multihit():
-    """Loads the instanced all-hits library (libshray_instance_multihit.so: depends on libshray_instance.so too)."""
-    return _load_client(INSTANCE_MULTIHIT_LIB, INSTANCE_MULTIHIT_SYMBOLS)
-
-
-def load_instance_point():
-    """Loads the instanced closest-point library (libshray_instance_point.so: depends on libshray_instance.so too)."""
-    return _load_client(INSTANCE_POINT_LIB, INSTANCE_POINT_SYMBOLS)
-
-
-def load_instance_near():
-    """Loads the instanced within-radius library (libshray_instance_near.so: depends on libshray_instance.so too)."""
-    return _load_client(INSTANCE_NEAR_LIB, INSTANCE_NEAR_SYMBOLS)
-
-
-def load_instance_overlap():
-    """Loads the instanced box-overlap library (libshray_instance_overlap.so: depends on libshray_instance.so too)."""
-    return _load_client(INSTANCE_OVERLAP_LIB, INSTANCE_OVERLAP_SYMBOLS)
-
-
-def load_instance_intersect():
-    """Loads the instanced triangle-intersection library (libshray_instance_intersect.so: depends on libshray_instance.so too)."""
-    return _load_client(INSTANCE_INTERSECT_LIB, INSTANCE_INTERSECT_SYMBOLS)
-
-
-def load_instance_clearance():
-    """Loads the instanced triangle-distance library (libshray_instance_clearance.so: depends on libshray_instance.so too)."""
-    return _load_client(INSTANCE_CLEARANCE_LIB, INSTANCE_CLEARANCE_SYMBOLS)
-
-
-def load_instance_pairs():
-    """Loads the instance-pair collision-matrix library (libshray_instance_pairs.so: depends on libshray_instance.so too)."""
-    return _load_client(INSTANCE_PAIRS_LIB, INSTANCE_PAIRS_SYMBOLS)
-
-
-def load_instance_sdf():
-    """Loads the instanced signed-distance library (libshray_instance_sdf.so: depends on libshray_instance.so,
-    libshray_instance_point.so and libshray_sdf.so too)."""
-    return _load_client(INSTANCE_SDF_LIB, INSTANCE_SDF_SYMBOLS)
-
-
-def load_instance_winding():
-    """Loads the instanced winding-number library (libshray_instance_winding.so: depends on libshray_instance.so,
-    libshray_instance_point.so and libshray_winding.so too)."""
-    return _load_client(INSTANCE_WINDING_LIB, INSTANCE_WINDING_SYMBOLS)
+def load_all():
+    """Loads the host library, the HIP layer and every client library, so a missing or mismatched one raises here."""
+    load_host()
+    load_hip()
+    for name, *_ in CLIENT_LIBRARIES:
+        globals()[f"load_{name}"]()
 
 
 def check_dist(code: int):

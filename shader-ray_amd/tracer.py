@@ -91,8 +91,7 @@ class Scene:
                          stream_ptr: int = 0, wait: bool = True):
         """Render + DMA into pinned host memory on a HIP stream (shray_render_host_async).  With wait=False
         the caller synchronises the stream before reading `pinned.array`."""
-        N.check(self._lib.shray_render_host_async(self._handle, C.byref(params), width, height, spp,
-                                                  C.c_void_p(pinned.ptr), C.c_void_p(stream_ptr)))
+        N.check(self._lib.shray_render_host_async(self._handle, C.byref(params), width, height, spp, C.c_void_p(pinned.ptr), _ptr(stream_ptr)))
         if wait:
             import torch
             torch.cuda.synchronize()
@@ -142,8 +141,7 @@ class Scene:
         """Asynchronous render into device memory (`out_ptr`, e.g. tensor.data_ptr()) on a
         HIP stream (`stream_ptr`, e.g. torch.cuda.current_stream().cuda_stream)."""
         N.check(self._lib.shray_render_device(
-            self._handle, C.byref(params), width, height, spp,
-            C.byref(tiles) if tiles is not None else None, C.c_void_p(out_ptr), C.c_void_p(stream_ptr)))
+            self._handle, C.byref(params), width, height, spp, C.byref(tiles) if tiles is not None else None, _ptr(out_ptr), _ptr(stream_ptr)))
 
     def trace_rays(self, rays, tmax=None, any_hit: bool = False, max_bvh_iterations: int = 400, max_leaf_tests: int = 10,
                    counters: bool = False):
@@ -151,16 +149,15 @@ class Scene:
         (origin, direction / the shray_ray layout); `tmax` (scalar or [n]) replaces the rays' own.  Returns a HIT_DTYPE array,
         and with counters=True also the walk's counters (shray_trace_rays_counters)."""
         rays = _host_rays(rays, tmax)
-        hits = np.empty(len(rays), HIT_DTYPE)
         qp = query_params(any_hit, max_bvh_iterations, max_leaf_tests)
         lib = N.load_query()
-        if counters:
-            c = N.Counters()
-            N.check(lib.shray_trace_rays_counters(self._handle, C.byref(qp), rays.ctypes.data_as(C.c_void_p), len(rays),
-                                                  hits.ctypes.data_as(C.c_void_p), C.byref(c)))
-            return hits, c.as_dict()
-        N.check(lib.shray_trace_rays(self._handle, C.byref(qp), rays.ctypes.data_as(C.c_void_p), len(rays), hits.ctypes.data_as(C.c_void_p)))
-        return hits
+        out = _blocking(self._handle, lib.shray_trace_rays, lib.shray_trace_rays_counters, (C.byref(qp),), rays, (),
+                        [_out(True, HIT_DTYPE, 4)], counters)
+        return out if counters else out[0]
+
+    def _items(self, kind: str, value=None):
+        """_per_item's converters of an items argument of `kind`, for the scene's device"""
+        return _converters(kind, self.device_index, "the scene", value)
 
     def trace_rays_into(self, rays_ptr: int, count: int, hits_ptr: int, stream_ptr: int = 0, any_hit: bool = False,
                         max_bvh_iterations: int = 400, max_leaf_tests: int = 10):
@@ -168,8 +165,7 @@ class Scene:
         (e.g. a float32 [n, 8] tensor's data_ptr()) -> `count` shray_hit records at `hits_ptr` (e.g. [n, 4] float32 / int32),
         on a HIP stream (`stream_ptr`, e.g. torch.cuda.current_stream().cuda_stream)."""
         qp = query_params(any_hit, max_bvh_iterations, max_leaf_tests)
-        N.check(N.load_query().shray_trace_rays_device(self._handle, C.byref(qp), C.c_void_p(rays_ptr), count, C.c_void_p(hits_ptr),
-                                                       C.c_void_p(stream_ptr)))
+        N.check(N.load_query().shray_trace_rays_device(self._handle, C.byref(qp), _ptr(rays_ptr), count, _ptr(hits_ptr), _ptr(stream_ptr)))
 
     def closest_points(self, points, max_dist2=None, counters: bool = False):
         """Closest-point queries (include/shader_ray_point.h): the nearest point of the surface to each point.  `points`: a
@@ -179,52 +175,15 @@ class Scene:
         a CLOSEST_DTYPE array for host points, an int32 [n, 8] tensor of shray_closest records (view it as float32 for q, dist2,
         u, v) for GPU points; with counters=True (host points only) also the walk's counters (shray_closest_points_counters)."""
         lib = N.load_point()
-        points = _host_if_cpu(points)
-        if _is_torch(points):
-            import torch
-            if counters:
-                raise ValueError("counters are counted on the host path: pass host points")
-            pts = self._device_points(points, max_dist2)
-            out = torch.empty((len(pts), 8), dtype=torch.int32, device=pts.device)
-            stream = torch.cuda.current_stream(pts.device)
-            N.check(lib.shray_closest_points_device(self._handle, C.c_void_p(pts.data_ptr()), len(pts), C.c_void_p(out.data_ptr()),
-                                                    C.c_void_p(stream.cuda_stream)))
-            return out
-        pts = _host_points(points, max_dist2)
-        out = np.empty(len(pts), CLOSEST_DTYPE)
-        if counters:
-            c = N.Counters()
-            N.check(lib.shray_closest_points_counters(self._handle, pts.ctypes.data_as(C.c_void_p), len(pts),
-                                                      out.ctypes.data_as(C.c_void_p), C.byref(c)))
-            return out, c.as_dict()
-        N.check(lib.shray_closest_points(self._handle, pts.ctypes.data_as(C.c_void_p), len(pts), out.ctypes.data_as(C.c_void_p)))
-        return out
+        out = _per_item(self._handle, (lib.shray_closest_points_device, lib.shray_closest_points, lib.shray_closest_points_counters), (),
+                        points, self._items("points", max_dist2), (), [_out(True, CLOSEST_DTYPE, 8)], counters)
+        return out if counters else out[0]
 
     def closest_points_into(self, points_ptr: int, count: int, out_ptr: int, stream_ptr: int = 0):
         """Asynchronous closest-point queries on device memory of the scene's device (shray_closest_points_device): `count`
         shray_point records at `points_ptr` (e.g. a float32 [n, 4] tensor's data_ptr()) -> `count` shray_closest records at
         `out_ptr` (e.g. [n, 8] int32 / float32), on a HIP stream (`stream_ptr`, e.g. torch.cuda.current_stream().cuda_stream)."""
-        N.check(N.load_point().shray_closest_points_device(self._handle, C.c_void_p(points_ptr), count, C.c_void_p(out_ptr),
-                                                           C.c_void_p(stream_ptr)))
-
-    def _device_points(self, points, max_dist2=None):
-        """a float32 [n, 3] / [n, 4] GPU tensor on the scene's device as a contiguous [n, 4] shray_point tensor (a copy when
-        `max_dist2` replaces the points' own)"""
-        import torch
-        if points.device.index != self.device_index():
-            raise ValueError(f"points are on {points.device}, the scene on cuda:{self.device_index()}")
-        if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] not in (3, 4):
-            raise ValueError("a GPU point tensor must be float32 [n, 3] (p) or [n, 4] (the shray_point layout)")
-        if points.shape[1] == 3:
-            pts = torch.empty((len(points), 4), dtype=torch.float32, device=points.device)
-            pts[:, :3] = points
-            pts[:, 3] = float("inf")
-        else:
-            pts = points.contiguous()
-        if max_dist2 is not None:
-            pts = pts.clone() if pts is points else pts
-            pts[:, 3] = torch.as_tensor(max_dist2, dtype=torch.float32, device=pts.device)
-        return pts
+        N.check(N.load_point().shray_closest_points_device(self._handle, _ptr(points_ptr), count, _ptr(out_ptr), _ptr(stream_ptr)))
 
     def signed_distance(self, points, max_dist2=None, closest: bool = False):
         """Signed distances to the surface (include/shader_ray_sdf.h): negative inside a closed, outward-wound mesh, NaN for a
@@ -233,29 +192,15 @@ class Scene:
         stream).  Returns float32 [n] of the same kind; with closest=True also the closest-point records (a CLOSEST_DTYPE array,
         or an int32 [n, 8] tensor)."""
         lib = N.load_sdf()
-        points = _host_if_cpu(points)
-        if _is_torch(points):
-            import torch
-            pts = self._device_points(points, max_dist2)
-            out = torch.empty(len(pts), dtype=torch.float32, device=pts.device)
-            rec = torch.empty((len(pts), 8), dtype=torch.int32, device=pts.device) if closest else None
-            stream = torch.cuda.current_stream(pts.device)
-            N.check(lib.shray_signed_distance_device(self._handle, C.c_void_p(pts.data_ptr()), len(pts), C.c_void_p(out.data_ptr()),
-                                                     C.c_void_p(rec.data_ptr() if closest else None), C.c_void_p(stream.cuda_stream)))
-            return (out, rec) if closest else out
-        pts = _host_points(points, max_dist2)
-        out = np.empty(len(pts), np.float32)
-        rec = np.empty(len(pts), CLOSEST_DTYPE) if closest else None
-        N.check(lib.shray_signed_distance(self._handle, pts.ctypes.data_as(C.c_void_p), len(pts), out.ctypes.data_as(C.c_void_p),
-                                          rec.ctypes.data_as(C.c_void_p) if closest else None))
-        return (out, rec) if closest else out
+        out = _per_item(self._handle, (lib.shray_signed_distance_device, lib.shray_signed_distance, None), (), points,
+                        self._items("points", max_dist2), (), [_out(True, np.float32), _out(closest, CLOSEST_DTYPE, 8)])
+        return out if closest else out[0]
 
     def signed_distance_into(self, points_ptr: int, count: int, out_ptr: int, closest_ptr: int = 0, stream_ptr: int = 0):
         """Asynchronous signed distance queries on device memory of the scene's device (shray_signed_distance_device): `count`
         shray_point records at `points_ptr` -> `count` float32 at `out_ptr` and, unless `closest_ptr` is 0, `count`
         shray_closest records there, on a HIP stream (`stream_ptr`, e.g. torch.cuda.current_stream().cuda_stream)."""
-        N.check(N.load_sdf().shray_signed_distance_device(self._handle, C.c_void_p(points_ptr), count, C.c_void_p(out_ptr),
-                                                          C.c_void_p(closest_ptr or None), C.c_void_p(stream_ptr)))
+        N.check(N.load_sdf().shray_signed_distance_device(self._handle, _ptr(points_ptr), count, _ptr(out_ptr), _ptr(closest_ptr), _ptr(stream_ptr)))
 
     def surface_info(self) -> dict:
         """The welded topology (shray_scene_surface_info): vertices, edges, boundary_edges, nonmanifold_edges,
@@ -280,55 +225,28 @@ class Scene:
         the scene's device (shray_winding_number_device, on the current torch stream).  `beta`: the far-field accuracy
         parameter, float('inf') for the exact sum over every triangle.  Returns float32 [n] of the same kind."""
         lib = N.load_winding()
-        points = _host_if_cpu(points)
-        if _is_torch(points):
-            import torch
-            pts = self._device_points(points)
-            out = torch.empty(len(pts), dtype=torch.float32, device=pts.device)
-            stream = torch.cuda.current_stream(pts.device)
-            N.check(lib.shray_winding_number_device(self._handle, C.c_void_p(pts.data_ptr()), len(pts), beta, C.c_void_p(out.data_ptr()),
-                                                    C.c_void_p(stream.cuda_stream)))
-            return out
-        pts = _host_points(points)
-        out = np.empty(len(pts), np.float32)
-        N.check(lib.shray_winding_number(self._handle, pts.ctypes.data_as(C.c_void_p), len(pts), beta, out.ctypes.data_as(C.c_void_p)))
-        return out
+        return _per_item(self._handle, (lib.shray_winding_number_device, lib.shray_winding_number, None), (), points, self._items("points"),
+                         (beta,), [_out(True, np.float32)])[0]
 
     def winding_number_into(self, points_ptr: int, count: int, out_ptr: int, beta: float = 2.0, stream_ptr: int = 0):
         """Asynchronous winding numbers on device memory of the scene's device (shray_winding_number_device): `count`
         shray_point records at `points_ptr` -> `count` float32 at `out_ptr`, on a HIP stream (`stream_ptr`)."""
-        N.check(N.load_winding().shray_winding_number_device(self._handle, C.c_void_p(points_ptr), count, beta, C.c_void_p(out_ptr),
-                                                             C.c_void_p(stream_ptr)))
+        N.check(N.load_winding().shray_winding_number_device(self._handle, _ptr(points_ptr), count, beta, _ptr(out_ptr), _ptr(stream_ptr)))
 
     def winding_signed_distance(self, points, max_dist2=None, beta: float = 2.0, closest: bool = False):
         """Signed distances whose sign comes from the winding number (shray_winding_signed_distance): negative where w > 0.5,
         NaN for a point with no triangle within its radius.  Arguments and results as for signed_distance."""
         lib = N.load_winding()
-        points = _host_if_cpu(points)
-        if _is_torch(points):
-            import torch
-            pts = self._device_points(points, max_dist2)
-            out = torch.empty(len(pts), dtype=torch.float32, device=pts.device)
-            rec = torch.empty((len(pts), 8), dtype=torch.int32, device=pts.device) if closest else None
-            stream = torch.cuda.current_stream(pts.device)
-            N.check(lib.shray_winding_signed_distance_device(self._handle, C.c_void_p(pts.data_ptr()), len(pts), beta,
-                                                             C.c_void_p(out.data_ptr()), C.c_void_p(rec.data_ptr() if closest else None),
-                                                             C.c_void_p(stream.cuda_stream)))
-            return (out, rec) if closest else out
-        pts = _host_points(points, max_dist2)
-        out = np.empty(len(pts), np.float32)
-        rec = np.empty(len(pts), CLOSEST_DTYPE) if closest else None
-        N.check(lib.shray_winding_signed_distance(self._handle, pts.ctypes.data_as(C.c_void_p), len(pts), beta,
-                                                  out.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p) if closest else None))
-        return (out, rec) if closest else out
+        out = _per_item(self._handle, (lib.shray_winding_signed_distance_device, lib.shray_winding_signed_distance, None), (), points,
+                        self._items("points", max_dist2), (beta,), [_out(True, np.float32), _out(closest, CLOSEST_DTYPE, 8)])
+        return out if closest else out[0]
 
     def winding_signed_distance_into(self, points_ptr: int, count: int, out_ptr: int, closest_ptr: int = 0, beta: float = 2.0,
                                      stream_ptr: int = 0):
         """Asynchronous winding-signed distances on device memory (shray_winding_signed_distance_device), as
         signed_distance_into."""
-        N.check(N.load_winding().shray_winding_signed_distance_device(self._handle, C.c_void_p(points_ptr), count, beta,
-                                                                      C.c_void_p(out_ptr), C.c_void_p(closest_ptr or None),
-                                                                      C.c_void_p(stream_ptr)))
+        N.check(N.load_winding().shray_winding_signed_distance_device(self._handle, _ptr(points_ptr), count, beta, _ptr(out_ptr), _ptr(closest_ptr),
+                                                                      _ptr(stream_ptr)))
 
     def winding_data(self) -> np.ndarray:
         """The derived node records (shray_scene_winding_data_download): float32 [nodes, 20] in packed pre-order: P, r, N, A,
@@ -350,8 +268,8 @@ class Scene:
         returns the counters of the walk that skips nothing (shray_trace_all_hits_counters)."""
         lib = N.load_multihit()
         return _first_k(self._handle, (lib.shray_trace_all_hits_device, lib.shray_trace_all_hits, lib.shray_trace_all_hits_counters),
-                        multihit_params(max_hits, max_leaf_tests), max_hits, "max_hits", rays, "rays",
-                        lambda r: _device_rays(r, self.device_index(), "the scene"), _host_rays, HIT_DTYPE, (4,), False, counts, counters)
+                        multihit_params(max_hits, max_leaf_tests), max_hits, "max_hits", rays, self._items("rays"), HIT_DTYPE, (4,), False,
+                        counts, counters)
 
     def trace_all_hits_into(self, rays_ptr: int, count: int, hits_ptr: int, counts_ptr: int = 0, max_hits: int = 8, stream_ptr: int = 0,
                             max_leaf_tests: int = 10):
@@ -359,9 +277,8 @@ class Scene:
         shray_ray records at `rays_ptr` -> count * max_hits shray_hit records at `hits_ptr` (0 iff max_hits is 0) and, unless
         `counts_ptr` is 0, `count` int32 crossing counts there, on a HIP stream (`stream_ptr`)."""
         mp = multihit_params(max_hits, max_leaf_tests)
-        N.check(N.load_multihit().shray_trace_all_hits_device(self._handle, C.byref(mp), C.c_void_p(rays_ptr), count,
-                                                              C.c_void_p(hits_ptr or None), C.c_void_p(counts_ptr or None),
-                                                              C.c_void_p(stream_ptr)))
+        N.check(N.load_multihit().shray_trace_all_hits_device(self._handle, C.byref(mp), _ptr(rays_ptr), count, _ptr(hits_ptr), _ptr(counts_ptr),
+                                                              _ptr(stream_ptr)))
 
     def crossing_counts(self, rays, max_leaf_tests: int = 10):
         """How many surfaces each ray crosses before its tmax (trace_all_hits with max_hits = 0): int32 [n], numpy for host
@@ -380,17 +297,15 @@ class Scene:
         the walk that prunes only by max_dist2 (shray_near_triangles_counters)."""
         lib = N.load_near()
         return _first_k(self._handle, (lib.shray_near_triangles_device, lib.shray_near_triangles, lib.shray_near_triangles_counters),
-                        near_params(max_near), max_near, "max_near", points, "points", self._device_points, _host_points, CLOSEST_DTYPE, (8,),
-                        False, counts, counters)
+                        near_params(max_near), max_near, "max_near", points, self._items("points"), CLOSEST_DTYPE, (8,), False, counts, counters)
 
     def triangles_within_into(self, points_ptr: int, count: int, out_ptr: int, counts_ptr: int = 0, max_near: int = 8, stream_ptr: int = 0):
         """Asynchronous within-radius queries on device memory of the scene's device (shray_near_triangles_device): `count`
         shray_point records at `points_ptr` -> count * max_near shray_closest records at `out_ptr` (0 iff max_near is 0) and,
         unless `counts_ptr` is 0, `count` int32 near counts there, on a HIP stream (`stream_ptr`)."""
         np_ = near_params(max_near)
-        N.check(N.load_near().shray_near_triangles_device(self._handle, C.byref(np_), C.c_void_p(points_ptr), count,
-                                                          C.c_void_p(out_ptr or None), C.c_void_p(counts_ptr or None),
-                                                          C.c_void_p(stream_ptr)))
+        N.check(N.load_near().shray_near_triangles_device(self._handle, C.byref(np_), _ptr(points_ptr), count, _ptr(out_ptr), _ptr(counts_ptr),
+                                                          _ptr(stream_ptr)))
 
     def near_counts(self, points):
         """How many triangles lie within each point's max_dist2 (triangles_within with max_near = 0): int32 [n], numpy for
@@ -409,22 +324,8 @@ class Scene:
         (shray_overlap_triangles_counters)."""
         lib = N.load_overlap()
         return _first_k(self._handle, (lib.shray_overlap_triangles_device, lib.shray_overlap_triangles, lib.shray_overlap_triangles_counters),
-                        overlap_params(max_triangles, any_only), max_triangles, "max_triangles", boxes, "boxes", self._device_boxes,
-                        _host_boxes, np.int32, (), False, counts, counters)
-
-    def _device_boxes(self, boxes):
-        """a float32 [n, 6] / [n, 8] GPU tensor on the scene's device as a contiguous [n, 8] shray_box tensor"""
-        import torch
-        if boxes.device.index != self.device_index():
-            raise ValueError(f"boxes are on {boxes.device}, the scene on cuda:{self.device_index()}")
-        if boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] not in (6, 8):
-            raise ValueError("a GPU box tensor must be float32 [n, 6] (lo, hi) or [n, 8] (the shray_box layout)")
-        if boxes.shape[1] == 8:
-            return boxes.contiguous()
-        bx = torch.zeros((len(boxes), 8), dtype=torch.float32, device=boxes.device)
-        bx[:, 0:3] = boxes[:, 0:3]
-        bx[:, 4:7] = boxes[:, 3:6]
-        return bx
+                        overlap_params(max_triangles, any_only), max_triangles, "max_triangles", boxes, self._items("boxes"), np.int32, (), False,
+                        counts, counters)
 
     def triangles_in_boxes_into(self, boxes_ptr: int, count: int, out_ptr: int, counts_ptr: int = 0, max_triangles: int = 8,
                                 any_only: bool = False, stream_ptr: int = 0):
@@ -432,9 +333,8 @@ class Scene:
         shray_box records at `boxes_ptr` -> count * max_triangles int32 indices at `out_ptr` (0 iff max_triangles is 0) and,
         unless `counts_ptr` is 0, `count` int32 counts there, on a HIP stream (`stream_ptr`)."""
         op = overlap_params(max_triangles, any_only)
-        N.check(N.load_overlap().shray_overlap_triangles_device(self._handle, C.byref(op), C.c_void_p(boxes_ptr), count,
-                                                                C.c_void_p(out_ptr or None), C.c_void_p(counts_ptr or None),
-                                                                C.c_void_p(stream_ptr)))
+        N.check(N.load_overlap().shray_overlap_triangles_device(self._handle, C.byref(op), _ptr(boxes_ptr), count, _ptr(out_ptr), _ptr(counts_ptr),
+                                                                _ptr(stream_ptr)))
 
     def box_counts(self, boxes):
         """How many triangles touch each box (triangles_in_boxes with max_triangles = 0): int32 [n], numpy for host boxes, a
@@ -461,22 +361,8 @@ class Scene:
         lib = N.load_intersect()
         return _first_k(self._handle, (lib.shray_intersect_triangles_device, lib.shray_intersect_triangles,
                                        lib.shray_intersect_triangles_counters),
-                        intersect_params(max_triangles, any_only, skip_shared), max_triangles, "max_triangles", triangles, "triangles",
-                        self._device_triangles, _host_triangles, np.int32, (), False, counts, counters)
-
-    def _device_triangles(self, triangles):
-        """a float32 [n, 9] / [n, 12] GPU tensor on the scene's device as a contiguous [n, 12] shray_triangle tensor"""
-        import torch
-        if triangles.device.index != self.device_index():
-            raise ValueError(f"triangles are on {triangles.device}, the scene on cuda:{self.device_index()}")
-        if triangles.dtype != torch.float32 or triangles.dim() != 2 or triangles.shape[1] not in (9, 12):
-            raise ValueError("a GPU triangle tensor must be float32 [n, 9] (a, b, c) or [n, 12] (the shray_triangle layout)")
-        if triangles.shape[1] == 12:
-            return triangles.contiguous()
-        tr = torch.zeros((len(triangles), 12), dtype=torch.float32, device=triangles.device)
-        for corner in range(3):
-            tr[:, 4 * corner:4 * corner + 3] = triangles[:, 3 * corner:3 * corner + 3]
-        return tr
+                        intersect_params(max_triangles, any_only, skip_shared), max_triangles, "max_triangles", triangles,
+                        self._items("triangles"), np.int32, (), False, counts, counters)
 
     def intersecting_triangles_into(self, triangles_ptr: int, count: int, out_ptr: int, counts_ptr: int = 0, max_triangles: int = 8,
                                     any_only: bool = False, skip_shared: bool = False, stream_ptr: int = 0):
@@ -485,9 +371,8 @@ class Scene:
         indices at `out_ptr` (0 iff max_triangles is 0) and, unless `counts_ptr` is 0, `count` int32 counts there, on a HIP
         stream (`stream_ptr`)."""
         op = intersect_params(max_triangles, any_only, skip_shared)
-        N.check(N.load_intersect().shray_intersect_triangles_device(self._handle, C.byref(op), C.c_void_p(triangles_ptr), count,
-                                                                    C.c_void_p(out_ptr or None), C.c_void_p(counts_ptr or None),
-                                                                    C.c_void_p(stream_ptr)))
+        N.check(N.load_intersect().shray_intersect_triangles_device(self._handle, C.byref(op), _ptr(triangles_ptr), count, _ptr(out_ptr),
+                                                                    _ptr(counts_ptr), _ptr(stream_ptr)))
 
     def intersection_counts(self, triangles, skip_shared: bool = False):
         """How many scene triangles each query triangle intersects (intersecting_triangles with max_triangles = 0): int32 [n],
@@ -513,30 +398,10 @@ class Scene:
         enqueued on the current torch stream (shray_intersect_self_device).  skip_shared defaults to True here: without it
         every triangle finds itself and its neighbours.  max_triangles = 0 returns None for the indices, counts=False None
         for the counts; any_only as for intersecting_triangles."""
-        if max_triangles == 0 and not counts:
-            raise ValueError("nothing is asked for: max_triangles is 0 and counts is False")
-        triangles = self.triangle_count()
-        if count is None:
-            count = max(triangles - first, 0)
-        op = intersect_params(max_triangles, any_only, skip_shared)
         lib = N.load_intersect()
-        rows = count if first >= 0 and 0 <= count <= triangles - first else 0   # (the library refuses any other range)
-        if device:
-            import torch
-            where = torch.device("cuda", self.device_index())
-            out = torch.empty((rows, max_triangles), dtype=torch.int32, device=where) if max_triangles > 0 else None
-            n = torch.empty((rows,), dtype=torch.int32, device=where) if counts else None
-            N.check(lib.shray_intersect_self_device(self._handle, C.byref(op), first, count,
-                                                    C.c_void_p(out.data_ptr() if out is not None else None),
-                                                    C.c_void_p(n.data_ptr() if n is not None else None),
-                                                    C.c_void_p(torch.cuda.current_stream(where).cuda_stream)))
-            return out, n
-        out = np.empty((rows, max_triangles), np.int32) if max_triangles > 0 else None
-        n = np.empty((rows,), np.int32) if counts else None
-        N.check(lib.shray_intersect_self(self._handle, C.byref(op), first, count,
-                                         out.ctypes.data_as(C.c_void_p) if out is not None else None,
-                                         n.ctypes.data_as(C.c_void_p) if n is not None else None))
-        return out, n
+        return _own_triangles(self._handle, (lib.shray_intersect_self_device, lib.shray_intersect_self),
+                              intersect_params(max_triangles, any_only, skip_shared), None, first, count, self.triangle_count,
+                              max_triangles, "max_triangles", np.int32, (), counts, device, self.device_index)
 
     def self_intersections_into(self, first: int, count: int, out_ptr: int, counts_ptr: int = 0, max_triangles: int = 8,
                                 any_only: bool = False, skip_shared: bool = True, stream_ptr: int = 0):
@@ -544,8 +409,8 @@ class Scene:
         -> count * max_triangles int32 indices at `out_ptr` (0 iff max_triangles is 0) and, unless `counts_ptr` is 0, `count`
         int32 counts there, device memory of the scene's device, on a HIP stream (`stream_ptr`)."""
         op = intersect_params(max_triangles, any_only, skip_shared)
-        N.check(N.load_intersect().shray_intersect_self_device(self._handle, C.byref(op), first, count, C.c_void_p(out_ptr or None),
-                                                               C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+        N.check(N.load_intersect().shray_intersect_self_device(self._handle, C.byref(op), first, count, _ptr(out_ptr),
+                                                               _ptr(counts_ptr), _ptr(stream_ptr)))
 
     def is_self_intersecting(self) -> bool:
         """Whether any triangle of the scene intersects one it shares no corner with (SHRAY_INTERSECT_ANY |
@@ -575,8 +440,8 @@ class Scene:
         lib = N.load_clearance()
         return _first_k(self._handle, (lib.shray_clearance_triangles_device, lib.shray_clearance_triangles,
                                        lib.shray_clearance_triangles_counters),
-                        clearance_params(max_pairs, max_dist2, any_only, skip_shared), max_pairs, "max_pairs", triangles, "triangles",
-                        self._device_triangles, _host_triangles, PAIR_DISTANCE_DTYPE, (12,), False, counts, counters)
+                        clearance_params(max_pairs, max_dist2, any_only, skip_shared), max_pairs, "max_pairs", triangles,
+                        self._items("triangles"), PAIR_DISTANCE_DTYPE, (12,), False, counts, counters)
 
     def triangle_distances_into(self, triangles_ptr: int, count: int, out_ptr: int, counts_ptr: int = 0, max_dist2: float = float("inf"),
                                 max_pairs: int = 1, any_only: bool = False, skip_shared: bool = False, stream_ptr: int = 0):
@@ -584,9 +449,8 @@ class Scene:
         `count` shray_triangle records at `triangles_ptr` -> count * max_pairs shray_pair_distance records at `out_ptr` (0 iff
         max_pairs is 0) and, unless `counts_ptr` is 0, `count` int32 counts there, on a HIP stream (`stream_ptr`)."""
         op = clearance_params(max_pairs, max_dist2, any_only, skip_shared)
-        N.check(N.load_clearance().shray_clearance_triangles_device(self._handle, C.byref(op), C.c_void_p(triangles_ptr), count,
-                                                                    C.c_void_p(out_ptr or None), C.c_void_p(counts_ptr or None),
-                                                                    C.c_void_p(stream_ptr)))
+        N.check(N.load_clearance().shray_clearance_triangles_device(self._handle, C.byref(op), _ptr(triangles_ptr), count, _ptr(out_ptr),
+                                                                    _ptr(counts_ptr), _ptr(stream_ptr)))
 
     def clearance_counts(self, triangles, max_dist2: float, skip_shared: bool = False):
         """How many scene triangles lie within `max_dist2` of each query triangle (triangle_distances with max_pairs = 0):
@@ -607,30 +471,10 @@ class Scene:
         torch stream (shray_clearance_self_device).  skip_shared defaults to True here: without it every triangle finds
         itself and its neighbours at distance 0.  max_pairs = 0 returns None for the records, counts=False None for the
         counts; any_only as for triangle_distances."""
-        if max_pairs == 0 and not counts:
-            raise ValueError("nothing is asked for: max_pairs is 0 and counts is False")
-        triangles = self.triangle_count()
-        if count is None:
-            count = max(triangles - first, 0)
-        op = clearance_params(max_pairs, max_dist2, any_only, skip_shared)
         lib = N.load_clearance()
-        rows = count if first >= 0 and 0 <= count <= triangles - first else 0   # (the library refuses any other range)
-        if device:
-            import torch
-            where = torch.device("cuda", self.device_index())
-            out = torch.empty((rows, max_pairs, 12), dtype=torch.int32, device=where) if max_pairs > 0 else None
-            n = torch.empty((rows,), dtype=torch.int32, device=where) if counts else None
-            N.check(lib.shray_clearance_self_device(self._handle, C.byref(op), first, count,
-                                                    C.c_void_p(out.data_ptr() if out is not None else None),
-                                                    C.c_void_p(n.data_ptr() if n is not None else None),
-                                                    C.c_void_p(torch.cuda.current_stream(where).cuda_stream)))
-            return out, n
-        out = np.empty((rows, max_pairs), PAIR_DISTANCE_DTYPE) if max_pairs > 0 else None
-        n = np.empty((rows,), np.int32) if counts else None
-        N.check(lib.shray_clearance_self(self._handle, C.byref(op), first, count,
-                                         out.ctypes.data_as(C.c_void_p) if out is not None else None,
-                                         n.ctypes.data_as(C.c_void_p) if n is not None else None))
-        return out, n
+        return _own_triangles(self._handle, (lib.shray_clearance_self_device, lib.shray_clearance_self),
+                              clearance_params(max_pairs, max_dist2, any_only, skip_shared), None, first, count, self.triangle_count,
+                              max_pairs, "max_pairs", PAIR_DISTANCE_DTYPE, (12,), counts, device, self.device_index)
 
     def self_clearance_into(self, first: int, count: int, out_ptr: int, counts_ptr: int = 0, max_dist2: float = float("inf"),
                             max_pairs: int = 1, any_only: bool = False, skip_shared: bool = True, stream_ptr: int = 0):
@@ -638,8 +482,8 @@ class Scene:
         count * max_pairs shray_pair_distance records at `out_ptr` (0 iff max_pairs is 0) and, unless `counts_ptr` is 0,
         `count` int32 counts there, device memory of the scene's device, on a HIP stream (`stream_ptr`)."""
         op = clearance_params(max_pairs, max_dist2, any_only, skip_shared)
-        N.check(N.load_clearance().shray_clearance_self_device(self._handle, C.byref(op), first, count, C.c_void_p(out_ptr or None),
-                                                               C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+        N.check(N.load_clearance().shray_clearance_self_device(self._handle, C.byref(op), first, count, _ptr(out_ptr),
+                                                               _ptr(counts_ptr), _ptr(stream_ptr)))
 
     def distance_to(self, other: "Scene", max_dist2: float = float("inf"), max_pairs: int = 1, counts: bool = True,
                     skip_shared: bool = False):
@@ -723,7 +567,7 @@ class Scene:
                 keep.append(tv)
         stats = N.RefitStats()
         if device:
-            N.check(lib.shray_scene_refit_device(self._handle, C.byref(inp), C.byref(stats), C.c_void_p(stream_ptr)))
+            N.check(lib.shray_scene_refit_device(self._handle, C.byref(inp), C.byref(stats), _ptr(stream_ptr)))
         else:
             N.check(lib.shray_scene_refit(self._handle, C.byref(inp), C.byref(stats)))
         return stats.as_dict()
@@ -752,9 +596,8 @@ class Scene:
         count = len(params_list)
         array = (N.FrameParams * count)(*params_list)
         N.check(self._lib.shray_render_batch_device(
-            self._handle, array, count, width, height, spp,
-            C.byref(tiles) if tiles is not None else None, C.c_void_p(out_ptr), frame_stride_bytes,
-            C.c_void_p(stream_ptr)))
+            self._handle, array, count, width, height, spp, C.byref(tiles) if tiles is not None else None, _ptr(out_ptr), frame_stride_bytes,
+            _ptr(stream_ptr)))
 
 
 def _is_torch(a) -> bool:
@@ -766,52 +609,164 @@ def _host_if_cpu(a):
     return a.detach().numpy() if _is_torch(a) and not a.is_cuda else a
 
 
-def _device_rays(rays, device_index: int, owner: str):
-    """a float32 [n, 8] GPU tensor on the device of `owner` ("the scene", "the set") as a contiguous shray_ray tensor"""
+def _ptr(address):
+    """an address (a data_ptr(), an int argument of an _into method) as a pointer argument; 0 and None are NULL"""
+    return C.c_void_p(address or None)
+
+
+def _on_device(tensor, device_index: int, owner: str, kind: str, name: str, widths, forms: str):
+    """The device-side converters' checks: `tensor` (`kind`: "rays", "points", ...) is on the device of `owner` ("the scene",
+    "the set") and is float32 [n, w] with w among `widths`.  Returns torch."""
     import torch
-    if rays.device.index != device_index:
-        raise ValueError(f"rays are on {rays.device}, {owner} on cuda:{device_index}")
-    if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-        raise ValueError("a GPU ray tensor must be float32 [n, 8] (the shray_ray layout)")
-    return rays.contiguous()
+    if tensor.device.index != device_index:
+        raise ValueError(f"{kind} are on {tensor.device}, {owner} on cuda:{device_index}")
+    if tensor.dtype != torch.float32 or tensor.dim() != 2 or tensor.shape[1] not in widths:
+        raise ValueError(f"a GPU {name} tensor must be float32 {forms}")
+    return torch
 
 
-def _first_k(handle, functions, params, k: int, k_name: str, items, kind: str, on_device, on_host, record_dtype, trailing, second: bool,
-             counts: bool, counters: bool):
-    """The counted first-K queries (all-hits rays, their instanced form, within-radius, box-overlap, triangle-intersection, triangle-distance): per item a
-    count and its first `k` records.  `functions`: the library's device form, blocking form and blocking form with counters, called with
-    (`handle`, `params`, items, n, records[, second], counts, ...).  `items` (`kind`: "rays", "points", "boxes"): a GPU tensor
-    takes the device path on the current torch stream, through `on_device` (which refuses another device or layout), anything
-    else the blocking path, through `on_host`.  The records are an int32 [n, k, *trailing] tensor or a `record_dtype` [n, k]
-    array, None when `k` is 0; with `second` an int32 [n, k] output follows them (the instances); the counts are int32 [n],
-    None unless `counts`.  Returns (records[, second], counts[, counters])."""
-    device_form, host_form, counters_form = functions
-    if k == 0 and not counts:
-        raise ValueError(f"nothing is asked for: {k_name} is 0 and counts is False")
-    items = _host_if_cpu(items)
-    if _is_torch(items):
+def _replaced(tensor, given, column: int, value):
+    """`tensor` with `value` (a scalar or [n]) in `column`, unless it is None: in a copy where `tensor` is the caller's own"""
+    if value is not None:
         import torch
-        if counters:
-            raise ValueError(f"counters are counted on the host path: pass host {kind}")
-        d = on_device(items)
-        new = lambda want, *shape: torch.empty((len(d), *shape), dtype=torch.int32, device=d.device) if want else None
-        outs = [new(k > 0, k, *trailing)] + ([new(k > 0, k)] if second else []) + [new(counts)]
-        stream = torch.cuda.current_stream(d.device)
-        d.record_stream(stream)   # (the query reads it after this call returns)
-        N.check(device_form(handle, C.byref(params), C.c_void_p(d.data_ptr()), len(d),
-                            *(C.c_void_p(o.data_ptr() if o is not None else None) for o in outs), C.c_void_p(stream.cuda_stream)))
-        return tuple(outs)
-    d = on_host(items)
-    new = lambda want, dtype, *shape: np.empty((len(d), *shape), dtype) if want else None   # (the library refuses a negative k)
-    outs = [new(k > 0, record_dtype, k)] + ([new(k > 0, np.int32, k)] if second else []) + [new(counts, np.int32)]
-    args = (handle, C.byref(params), d.ctypes.data_as(C.c_void_p), len(d),
-            *(o.ctypes.data_as(C.c_void_p) if o is not None else None for o in outs))
+        tensor = tensor.clone() if tensor is given else tensor
+        tensor[:, column] = torch.as_tensor(value, dtype=torch.float32, device=tensor.device)
+    return tensor
+
+
+def _device_rays(rays, device_index: int, owner: str, tmax=None):
+    """a float32 [n, 8] GPU tensor on the device of `owner` as a contiguous shray_ray tensor (a copy when `tmax` replaces the
+    rays' own)"""
+    _on_device(rays, device_index, owner, "rays", "ray", (8,), "[n, 8] (the shray_ray layout)")
+    return _replaced(rays.contiguous(), rays, 3, tmax)
+
+
+def _device_points(points, device_index: int, owner: str, max_dist2=None):
+    """a float32 [n, 3] / [n, 4] GPU tensor on the device of `owner` as a contiguous [n, 4] shray_point tensor (a copy when
+    `max_dist2` replaces the points' own)"""
+    torch = _on_device(points, device_index, owner, "points", "point", (3, 4), "[n, 3] (p) or [n, 4] (the shray_point layout)")
+    if points.shape[1] == 3:
+        pts = torch.empty((len(points), 4), dtype=torch.float32, device=points.device)
+        pts[:, :3] = points
+        pts[:, 3] = float("inf")
+    else:
+        pts = points.contiguous()
+    return _replaced(pts, points, 3, max_dist2)
+
+
+def _device_boxes(boxes, device_index: int, owner: str):
+    """a float32 [n, 6] / [n, 8] GPU tensor on the device of `owner` as a contiguous [n, 8] shray_box tensor"""
+    torch = _on_device(boxes, device_index, owner, "boxes", "box", (6, 8), "[n, 6] (lo, hi) or [n, 8] (the shray_box layout)")
+    if boxes.shape[1] == 8:
+        return boxes.contiguous()
+    bx = torch.zeros((len(boxes), 8), dtype=torch.float32, device=boxes.device)
+    bx[:, 0:3] = boxes[:, 0:3]
+    bx[:, 4:7] = boxes[:, 3:6]
+    return bx
+
+
+def _device_triangles(triangles, device_index: int, owner: str):
+    """a float32 [n, 9] / [n, 12] GPU tensor on the device of `owner` as a contiguous [n, 12] shray_triangle tensor"""
+    torch = _on_device(triangles, device_index, owner, "triangles", "triangle", (9, 12),
+                       "[n, 9] (a, b, c) or [n, 12] (the shray_triangle layout)")
+    if triangles.shape[1] == 12:
+        return triangles.contiguous()
+    tr = torch.zeros((len(triangles), 12), dtype=torch.float32, device=triangles.device)
+    for corner in range(3):
+        tr[:, 4 * corner:4 * corner + 3] = triangles[:, 3 * corner:3 * corner + 3]
+    return tr
+
+
+def _out(want, dtype, *trailing, k=None):
+    """An output of _per_item and _own_triangles: wanted or not, then per item `dtype` records (`k` of them, unless None) in
+    an array, int32 / float32 [*trailing] ([k, *trailing]) in a tensor."""
+    lead = () if k is None else (k,)
+    return bool(want), dtype, lead, lead + trailing
+
+
+def _new_outputs(outs, rows: int, device=None):
+    """the wanted ones of `outs` (_out) with `rows` rows each, None for the others: arrays, or with `device` tensors there"""
+    if device is None:
+        return [np.empty((rows, *shape), dtype) if want else None for want, dtype, shape, _ in outs]
+    import torch
+    return [torch.empty((rows, *shape), dtype=torch.float32 if dtype is np.float32 else torch.int32, device=device) if want else None
+            for want, dtype, _, shape in outs]
+
+
+def _blocking(handle, host_form, counters_form, lead, d, after, outs, counters: bool = False):
+    """_per_item's host half: `d` is the converted array of items."""
+    got = _new_outputs(outs, len(d))
+    args = (handle, *lead, d.ctypes.data_as(C.c_void_p), len(d), *after,
+            *(o.ctypes.data_as(C.c_void_p) if o is not None else None for o in got))
     if counters:
         c = N.Counters()
         N.check(counters_form(*args, C.byref(c)))
-        return (*outs, c.as_dict())
+        return (*got, c.as_dict())
     N.check(host_form(*args))
-    return tuple(outs)
+    return tuple(got)
+
+
+def _per_item(handle, forms, lead, items, converters, after, outs, counters: bool = False):
+    """Items in, per-item outputs out: the one marshalling path of the queries that take an items argument.  `forms`: the
+    library's device form, blocking form and blocking form with counters (None where it has none), called with (`handle`,
+    *`lead`, items, n, *`after`, an address or NULL per output[, the stream | the counters]).  `items`: a GPU tensor takes the
+    device path on the current torch stream of its device, anything else (a CPU tensor as numpy) the blocking path;
+    `converters` (_converters) names the kind and makes of either the library's layout, refusing another device or form.
+    `outs`: an _out per output.  `counters` are refused on the device path.  Returns the outputs in order, None for those
+    not wanted, as tensors or arrays[, then the counters as a dict]."""
+    kind, on_device, on_host = converters
+    items = _host_if_cpu(items)
+    if not _is_torch(items):
+        return _blocking(handle, forms[1], forms[2], lead, on_host(items), after, outs, counters)
+    import torch
+    if counters:
+        raise ValueError(f"counters are counted on the host path: pass host {kind}")
+    d = on_device(items)
+    got = _new_outputs(outs, len(d), d.device)
+    stream = torch.cuda.current_stream(d.device)
+    d.record_stream(stream)   # (the query reads it after this call returns)
+    N.check(forms[0](handle, *lead, _ptr(d.data_ptr()), len(d), *after, *(_ptr(None if o is None else o.data_ptr()) for o in got),
+                     _ptr(stream.cuda_stream)))
+    return tuple(got)
+
+
+def _first_k(handle, functions, params, k: int, k_name: str, items, converters, record_dtype, trailing, second: bool, counts: bool,
+             counters: bool):
+    """The counted first-K queries (all-hits rays, within-radius, box-overlap, triangle-intersection, triangle-distance, and
+    their instanced forms) through _per_item: per item a count and its first `k` records.  The records are an int32 [n, k,
+    *trailing] tensor or a `record_dtype` [n, k] array, None when `k` is 0 (the library refuses a negative k); with `second`
+    an int32 [n, k] output follows them (the instances); the counts are int32 [n], None unless `counts`.  Returns
+    (records[, second], counts[, counters])."""
+    if k == 0 and not counts:
+        raise ValueError(f"nothing is asked for: {k_name} is 0 and counts is False")
+    outs = [_out(k > 0, record_dtype, *trailing, k=k)] + ([_out(k > 0, np.int32, k=k)] if second else []) + [_out(counts, np.int32)]
+    return _per_item(handle, functions, (C.byref(params),), items, converters, (), outs, counters)
+
+
+def _own_triangles(handle, forms, params, instance, first: int, count, triangles, k: int, k_name: str, record_dtype, trailing,
+                   counts: bool, device: bool, device_index):
+    """The range forms: the queries are an owner's own triangles [first, first + count) (count None: up to the last of its
+    `triangles()`), of instance `instance` of a set or (None) of a scene.  `forms`: the library's device and blocking form,
+    called with (`handle`, `params`[, instance], first, count, records[, instances], counts[, the stream]).  Returns
+    (records[, instances], counts) as _first_k does, arrays or with `device` tensors on cuda:`device_index()` enqueued on
+    the current torch stream, of `rows` rows: `count`, or 0 for a range the library refuses."""
+    if k == 0 and not counts:
+        raise ValueError(f"nothing is asked for: {k_name} is 0 and counts is False")
+    total = triangles()
+    if count is None:
+        count = max(total - first, 0)
+    rows = count if first >= 0 and 0 <= count <= total - first else 0
+    outs = [_out(k > 0, record_dtype, *trailing, k=k)] + ([_out(k > 0, np.int32, k=k)] if instance is not None else []) + [_out(counts, np.int32)]
+    args = (handle, C.byref(params), *(() if instance is None else (instance,)), first, count)
+    if not device:
+        got = _new_outputs(outs, rows)
+        N.check(forms[1](*args, *(o.ctypes.data_as(C.c_void_p) if o is not None else None for o in got)))
+        return tuple(got)
+    import torch
+    where = torch.device("cuda", device_index())
+    got = _new_outputs(outs, max(rows, 1), where)   # (an empty tensor has no pointer: one row is allocated for an empty range)
+    N.check(forms[0](*args, *(_ptr(None if o is None else o.data_ptr()) for o in got), _ptr(torch.cuda.current_stream(where).cuda_stream)))
+    return tuple(None if o is None else o[:rows] for o in got)
 
 
 # a ray buffer / hit array of the query (include/shader_ray_query.h): 32 and 16 bytes per element
@@ -1014,6 +969,20 @@ def _host_boxes(boxes) -> np.ndarray:
     """Scene.triangles_in_boxes's host box forms as one contiguous BOX_DTYPE array."""
     return _host_records(boxes, BOX_DTYPE, 6, 8, lambda a: make_boxes(a[:, 0:3], a[:, 3:6]), None, None,
                          "boxes must be a BOX_DTYPE array or [n, 6] (lo, hi) / [n, 8] (shray_box) float32")
+
+
+# the item kinds of the queries: kind -> (the device-side converter, the host-side converter)
+_CONVERTERS = {"rays": (_device_rays, _host_rays), "points": (_device_points, _host_points), "boxes": (_device_boxes, _host_boxes),
+               "triangles": (_device_triangles, _host_triangles)}
+
+
+def _converters(kind: str, device_index, owner: str, value=None):
+    """_per_item's converters of an items argument: (`kind`, the device-side one, the host-side one).  `device_index`: a
+    callable, asked on the device path only; `value`, unless None, replaces the rays' tmax / the points' max_dist2."""
+    on_device, on_host = _CONVERTERS[kind]
+    if value is None:
+        return kind, lambda tensor: on_device(tensor, device_index(), owner), on_host
+    return kind, lambda tensor: on_device(tensor, device_index(), owner, value), lambda array: on_host(array, value)
 
 
 def voxel_boxes(origin, cell, dims, device=None):
@@ -1276,7 +1245,7 @@ class InstanceSet:
         """The asynchronous update on device memory of the set's device (shray_instance_set_update_device): count * 12 float32
         object-to-world maps at `transforms_ptr`, or 0 to keep the current ones, on a HIP stream (`stream_ptr`, e.g.
         torch.cuda.current_stream().cuda_stream).  The array must stay alive until the update has run."""
-        N.check(self._lib.shray_instance_set_update_device(self._handle, C.c_void_p(transforms_ptr or None), C.c_void_p(stream_ptr)))
+        N.check(self._lib.shray_instance_set_update_device(self._handle, _ptr(transforms_ptr), _ptr(stream_ptr)))
 
     def update_status(self) -> int:
         """Waits for the most recent device update: -1 if it was applied (or none was made), else the lowest instance index whose
@@ -1297,38 +1266,16 @@ class InstanceSet:
         the device path; one on another device is refused.  Returns (hits: HIT_DTYPE, instances: int32), and with counters=True
         also the walks' counters."""
         qp = query_params(any_hit, max_bvh_iterations, max_leaf_tests)
-        rays = _host_if_cpu(rays)
-        if _is_torch(rays):
-            import torch
-            if rays.device.index != self.device:
-                raise ValueError(f"rays are on {rays.device}, the set on cuda:{self.device}")
-            if counters:
-                raise ValueError("counters are counted on the host path: pass host rays")
-            r = rays if tmax is None else rays.clone()
-            if r.dtype != torch.float32 or r.dim() != 2 or r.shape[1] != 8:
-                raise ValueError("a GPU ray tensor must be float32 [n, 8] (the shray_ray layout)")
-            r = r.contiguous()
-            if tmax is not None:
-                r[:, 3] = torch.as_tensor(tmax, dtype=torch.float32, device=r.device)
-            hits = torch.empty((len(r), 4), dtype=torch.int32, device=r.device)
-            inst = torch.empty(len(r), dtype=torch.int32, device=r.device)
-            stream = torch.cuda.current_stream(r.device)
-            N.check(self._lib.shray_trace_instances_device(self._handle, C.byref(qp), C.c_void_p(r.data_ptr()), len(r),
-                                                           C.c_void_p(hits.data_ptr()), C.c_void_p(inst.data_ptr()),
-                                                           C.c_void_p(stream.cuda_stream)))
-            stream.synchronize()
-            return np.ascontiguousarray(hits.cpu().numpy()).view(HIT_DTYPE).reshape(-1), inst.cpu().numpy()
-        rays = _host_rays(rays, tmax)
-        hits = np.empty(len(rays), HIT_DTYPE)
-        inst = np.empty(len(rays), np.int32)
-        args = (self._handle, C.byref(qp), rays.ctypes.data_as(C.c_void_p), len(rays), hits.ctypes.data_as(C.c_void_p),
-                inst.ctypes.data_as(C.c_void_p))
-        if counters:
-            c = N.Counters()
-            N.check(self._lib.shray_trace_instances_counters(*args, C.byref(c)))
-            return hits, inst, c.as_dict()
-        N.check(self._lib.shray_trace_instances(*args))
-        return hits, inst
+        lib = self._lib
+        out = _per_item(self._handle, (lib.shray_trace_instances_device, lib.shray_trace_instances, lib.shray_trace_instances_counters),
+                        (C.byref(qp),), rays, self._items("rays", tmax), (), [_out(True, HIT_DTYPE, 4), _out(True, np.int32)], counters)
+        if _is_torch(out[0]):   # (the copies to the host wait for the query, on the stream it was enqueued on)
+            return np.ascontiguousarray(out[0].cpu().numpy()).view(HIT_DTYPE).reshape(-1), out[1].cpu().numpy()
+        return out
+
+    def _items(self, kind: str, value=None):
+        """_per_item's converters of an items argument of `kind`, for the set's device"""
+        return _converters(kind, lambda: self.device, "the set", value)
 
     def trace_rays_into(self, rays_ptr: int, count: int, hits_ptr: int, instances_ptr: int = 0, stream_ptr: int = 0,
                         any_hit: bool = False, max_bvh_iterations: int = 400, max_leaf_tests: int = 10):
@@ -1336,8 +1283,8 @@ class InstanceSet:
         shray_ray records at `rays_ptr` -> shray_hit records at `hits_ptr` and, unless `instances_ptr` is 0, int32 instance
         indices there, on a HIP stream (`stream_ptr`, e.g. torch.cuda.current_stream().cuda_stream)."""
         qp = query_params(any_hit, max_bvh_iterations, max_leaf_tests)
-        N.check(self._lib.shray_trace_instances_device(self._handle, C.byref(qp), C.c_void_p(rays_ptr), count, C.c_void_p(hits_ptr),
-                                                       C.c_void_p(instances_ptr or None), C.c_void_p(stream_ptr)))
+        N.check(self._lib.shray_trace_instances_device(self._handle, C.byref(qp), _ptr(rays_ptr), count, _ptr(hits_ptr),
+                                                       _ptr(instances_ptr), _ptr(stream_ptr)))
 
     def trace_all_hits(self, rays, max_hits: int = 8, counts: bool = True, max_leaf_tests: int = 10, counters: bool = False):
         """Instanced all-hits ray queries (include/shader_ray_instance_multihit.h): per world ray the number of surfaces it
@@ -1352,8 +1299,8 @@ class InstanceSet:
         lib = N.load_instance_multihit()
         return _first_k(self._handle, (lib.shray_trace_instances_all_hits_device, lib.shray_trace_instances_all_hits,
                                        lib.shray_trace_instances_all_hits_counters),
-                        multihit_params(max_hits, max_leaf_tests), max_hits, "max_hits", rays, "rays",
-                        lambda r: _device_rays(r, self.device, "the set"), _host_rays, HIT_DTYPE, (4,), True, counts, counters)
+                        multihit_params(max_hits, max_leaf_tests), max_hits, "max_hits", rays, self._items("rays"), HIT_DTYPE, (4,), True,
+                        counts, counters)
 
     def trace_all_hits_into(self, rays_ptr: int, count: int, hits_ptr: int, instances_ptr: int = 0, counts_ptr: int = 0,
                             max_hits: int = 8, stream_ptr: int = 0, max_leaf_tests: int = 10):
@@ -1363,8 +1310,7 @@ class InstanceSet:
         unless `counts_ptr` is 0 `count` int32 crossing counts there, on a HIP stream (`stream_ptr`)."""
         mp = multihit_params(max_hits, max_leaf_tests)
         N.check(N.load_instance_multihit().shray_trace_instances_all_hits_device(
-            self._handle, C.byref(mp), C.c_void_p(rays_ptr), count, C.c_void_p(hits_ptr or None), C.c_void_p(instances_ptr or None),
-            C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+            self._handle, C.byref(mp), _ptr(rays_ptr), count, _ptr(hits_ptr), _ptr(instances_ptr), _ptr(counts_ptr), _ptr(stream_ptr)))
 
     def crossing_counts(self, rays, max_leaf_tests: int = 10):
         """How many surfaces each world ray crosses before its tmax over all instances (trace_all_hits with max_hits = 0):
@@ -1379,37 +1325,16 @@ class InstanceSet:
         path on the current torch stream and returns (int32 [n, 8] tensor of shray_closest records, int32 [n] tensor).  A miss
         has instance -1.  counters=True (host points only) also returns the walks' counters."""
         lib = N.load_instance_point()
-        points = _host_if_cpu(points)
-        if _is_torch(points):
-            import torch
-            if counters:
-                raise ValueError("counters are counted on the host path: pass host points")
-            if points.device.index != self.device:
-                raise ValueError(f"points are on {points.device}, the set on cuda:{self.device}")
-            pts = self._scenes[0]._device_points(points, max_dist2)
-            out = torch.empty((len(pts), 8), dtype=torch.int32, device=pts.device)
-            inst = torch.empty(len(pts), dtype=torch.int32, device=pts.device)
-            stream = torch.cuda.current_stream(pts.device)
-            N.check(lib.shray_closest_points_instances_device(self._handle, C.c_void_p(pts.data_ptr()), len(pts), C.c_void_p(out.data_ptr()),
-                                                              C.c_void_p(inst.data_ptr()), C.c_void_p(stream.cuda_stream)))
-            return out, inst
-        pts = _host_points(points, max_dist2)
-        out = np.empty(len(pts), CLOSEST_DTYPE)
-        inst = np.empty(len(pts), np.int32)
-        args = (self._handle, pts.ctypes.data_as(C.c_void_p), len(pts), out.ctypes.data_as(C.c_void_p), inst.ctypes.data_as(C.c_void_p))
-        if counters:
-            c = N.Counters()
-            N.check(lib.shray_closest_points_instances_counters(*args, C.byref(c)))
-            return out, inst, c.as_dict()
-        N.check(lib.shray_closest_points_instances(*args))
-        return out, inst
+        return _per_item(self._handle, (lib.shray_closest_points_instances_device, lib.shray_closest_points_instances,
+                                        lib.shray_closest_points_instances_counters),
+                         (), points, self._items("points", max_dist2), (), [_out(True, CLOSEST_DTYPE, 8), _out(True, np.int32)], counters)
 
     def closest_points_into(self, points_ptr: int, count: int, out_ptr: int, instances_ptr: int = 0, stream_ptr: int = 0):
         """Asynchronous instanced closest-point queries on device memory of the set's device
         (shray_closest_points_instances_device): `count` shray_point records at `points_ptr` -> `count` shray_closest records at
         `out_ptr` and, unless `instances_ptr` is 0, int32 instance indices there, on a HIP stream (`stream_ptr`)."""
         N.check(N.load_instance_point().shray_closest_points_instances_device(
-            self._handle, C.c_void_p(points_ptr), count, C.c_void_p(out_ptr), C.c_void_p(instances_ptr or None), C.c_void_p(stream_ptr)))
+            self._handle, _ptr(points_ptr), count, _ptr(out_ptr), _ptr(instances_ptr), _ptr(stream_ptr)))
 
     def signed_distance(self, points, max_dist2=None, closest: bool = False, counters: bool = False):
         """Instanced signed distances (include/shader_ray_instance_sdf.h): per world-space point the distance to the nearest
@@ -1420,35 +1345,12 @@ class InstanceSet:
         [n] tensor.  With closest=True returns (values, records, instances), the last two as closest_points returns them.
         counters=True (host points only) also returns the counters of the sign walks, last."""
         lib = N.load_instance_sdf()
-        points = _host_if_cpu(points)
-        if _is_torch(points):
-            import torch
-            if counters:
-                raise ValueError("counters are counted on the host path: pass host points")
-            if points.device.index != self.device:
-                raise ValueError(f"points are on {points.device}, the set on cuda:{self.device}")
-            pts = self._scenes[0]._device_points(points, max_dist2)
-            out = torch.empty(len(pts), dtype=torch.float32, device=pts.device)
-            rec = torch.empty((len(pts), 8), dtype=torch.int32, device=pts.device) if closest else None
-            inst = torch.empty(len(pts), dtype=torch.int32, device=pts.device) if closest else None
-            stream = torch.cuda.current_stream(pts.device)
-            N.check(lib.shray_signed_distance_instances_device(
-                self._handle, C.c_void_p(pts.data_ptr()), len(pts), C.c_void_p(out.data_ptr()), C.c_void_p(rec.data_ptr() if closest else None),
-                C.c_void_p(inst.data_ptr() if closest else None), C.c_void_p(stream.cuda_stream)))
-            return (out, rec, inst) if closest else out
-        pts = _host_points(points, max_dist2)
-        out = np.empty(len(pts), np.float32)
-        rec = np.empty(len(pts), CLOSEST_DTYPE) if closest else None
-        inst = np.empty(len(pts), np.int32) if closest else None
-        args = (self._handle, pts.ctypes.data_as(C.c_void_p), len(pts), out.ctypes.data_as(C.c_void_p),
-                rec.ctypes.data_as(C.c_void_p) if closest else None, inst.ctypes.data_as(C.c_void_p) if closest else None)
-        result = (out, rec, inst) if closest else (out,)
-        if counters:
-            c = N.Counters()
-            N.check(lib.shray_signed_distance_instances_counters(*args, C.byref(c)))
-            return result + (c.as_dict(),)
-        N.check(lib.shray_signed_distance_instances(*args))
-        return result if closest else out
+        out = _per_item(self._handle, (lib.shray_signed_distance_instances_device, lib.shray_signed_distance_instances,
+                                       lib.shray_signed_distance_instances_counters),
+                        (), points, self._items("points", max_dist2), (),
+                        [_out(True, np.float32), _out(closest, CLOSEST_DTYPE, 8), _out(closest, np.int32)], counters)
+        out = out if closest else out[:1] + out[3:]   # (values[, records, instances][, counters])
+        return out if len(out) > 1 else out[0]
 
     def signed_distance_into(self, points_ptr: int, count: int, out_ptr: int, closest_ptr: int = 0, instances_ptr: int = 0,
                              stream_ptr: int = 0):
@@ -1457,8 +1359,7 @@ class InstanceSet:
         unless `closest_ptr` is 0 `count` shray_closest records there, and unless `instances_ptr` is 0 int32 instance indices
         there, on a HIP stream (`stream_ptr`)."""
         N.check(N.load_instance_sdf().shray_signed_distance_instances_device(
-            self._handle, C.c_void_p(points_ptr), count, C.c_void_p(out_ptr), C.c_void_p(closest_ptr or None),
-            C.c_void_p(instances_ptr or None), C.c_void_p(stream_ptr)))
+            self._handle, _ptr(points_ptr), count, _ptr(out_ptr), _ptr(closest_ptr), _ptr(instances_ptr), _ptr(stream_ptr)))
 
     def closed(self) -> bool:
         """Whether every member scene is closed (Scene.surface_info()["closed"]): what the sign's guarantee asks of them."""
@@ -1472,23 +1373,9 @@ class InstanceSet:
         tensor on the set's device takes the device path on the current torch stream and returns a float32 [n] tensor.  With
         containing=True returns (values, int32 [n]): the lowest instance whose own term is above 0.5, or -1."""
         lib = N.load_instance_winding()
-        points = _host_if_cpu(points)
-        if _is_torch(points):
-            import torch
-            pts = self._device_points(points)
-            out = torch.empty(len(pts), dtype=torch.float32, device=pts.device)
-            inside = torch.empty(len(pts), dtype=torch.int32, device=pts.device) if containing else None
-            stream = torch.cuda.current_stream(pts.device)
-            N.check(lib.shray_winding_number_instances_device(
-                self._handle, C.c_void_p(pts.data_ptr()), len(pts), beta, C.c_void_p(out.data_ptr()),
-                C.c_void_p(inside.data_ptr() if containing else None), C.c_void_p(stream.cuda_stream)))
-            return (out, inside) if containing else out
-        pts = _host_points(points)
-        out = np.empty(len(pts), np.float32)
-        inside = np.empty(len(pts), np.int32) if containing else None
-        N.check(lib.shray_winding_number_instances(self._handle, pts.ctypes.data_as(C.c_void_p), len(pts), beta, out.ctypes.data_as(C.c_void_p),
-                                                   inside.ctypes.data_as(C.c_void_p) if containing else None))
-        return (out, inside) if containing else out
+        out = _per_item(self._handle, (lib.shray_winding_number_instances_device, lib.shray_winding_number_instances, None), (), points,
+                        self._items("points"), (beta,), [_out(True, np.float32), _out(containing, np.int32)])
+        return out if containing else out[0]
 
     def winding_number_into(self, points_ptr: int, count: int, out_ptr: int, containing_ptr: int = 0, beta: float = 2.0,
                             stream_ptr: int = 0):
@@ -1496,44 +1383,24 @@ class InstanceSet:
         `count` shray_point records at `points_ptr` -> `count` float32 at `out_ptr` and, unless `containing_ptr` is 0, int32
         containing instances there, on a HIP stream (`stream_ptr`)."""
         N.check(N.load_instance_winding().shray_winding_number_instances_device(
-            self._handle, C.c_void_p(points_ptr), count, beta, C.c_void_p(out_ptr), C.c_void_p(containing_ptr or None), C.c_void_p(stream_ptr)))
+            self._handle, _ptr(points_ptr), count, beta, _ptr(out_ptr), _ptr(containing_ptr), _ptr(stream_ptr)))
 
     def winding_signed_distance(self, points, max_dist2=None, beta: float = 2.0, closest: bool = False):
         """Instanced signed distances whose sign comes from the summed winding number
         (shray_winding_signed_distance_instances): closest_points' record, negative where winding_number is above 0.5, the
         union's sign; NaN for a point with nothing within its radius.  Arguments and results as for signed_distance."""
         lib = N.load_instance_winding()
-        points = _host_if_cpu(points)
-        if _is_torch(points):
-            import torch
-            if points.device.index != self.device:
-                raise ValueError(f"points are on {points.device}, the set on cuda:{self.device}")
-            pts = self._scenes[0]._device_points(points, max_dist2)
-            out = torch.empty(len(pts), dtype=torch.float32, device=pts.device)
-            rec = torch.empty((len(pts), 8), dtype=torch.int32, device=pts.device) if closest else None
-            inst = torch.empty(len(pts), dtype=torch.int32, device=pts.device) if closest else None
-            stream = torch.cuda.current_stream(pts.device)
-            N.check(lib.shray_winding_signed_distance_instances_device(
-                self._handle, C.c_void_p(pts.data_ptr()), len(pts), beta, C.c_void_p(out.data_ptr()),
-                C.c_void_p(rec.data_ptr() if closest else None), C.c_void_p(inst.data_ptr() if closest else None),
-                C.c_void_p(stream.cuda_stream)))
-            return (out, rec, inst) if closest else out
-        pts = _host_points(points, max_dist2)
-        out = np.empty(len(pts), np.float32)
-        rec = np.empty(len(pts), CLOSEST_DTYPE) if closest else None
-        inst = np.empty(len(pts), np.int32) if closest else None
-        N.check(lib.shray_winding_signed_distance_instances(
-            self._handle, pts.ctypes.data_as(C.c_void_p), len(pts), beta, out.ctypes.data_as(C.c_void_p),
-            rec.ctypes.data_as(C.c_void_p) if closest else None, inst.ctypes.data_as(C.c_void_p) if closest else None))
-        return (out, rec, inst) if closest else out
+        out = _per_item(self._handle, (lib.shray_winding_signed_distance_instances_device, lib.shray_winding_signed_distance_instances, None),
+                        (), points, self._items("points", max_dist2), (beta,),
+                        [_out(True, np.float32), _out(closest, CLOSEST_DTYPE, 8), _out(closest, np.int32)])
+        return out if closest else out[0]
 
     def winding_signed_distance_into(self, points_ptr: int, count: int, out_ptr: int, closest_ptr: int = 0, instances_ptr: int = 0,
                                      beta: float = 2.0, stream_ptr: int = 0):
         """Asynchronous instanced winding-signed distances on device memory of the set's device
         (shray_winding_signed_distance_instances_device), as signed_distance_into."""
         N.check(N.load_instance_winding().shray_winding_signed_distance_instances_device(
-            self._handle, C.c_void_p(points_ptr), count, beta, C.c_void_p(out_ptr), C.c_void_p(closest_ptr or None),
-            C.c_void_p(instances_ptr or None), C.c_void_p(stream_ptr)))
+            self._handle, _ptr(points_ptr), count, beta, _ptr(out_ptr), _ptr(closest_ptr), _ptr(instances_ptr), _ptr(stream_ptr)))
 
     def orientations(self) -> np.ndarray:
         """The orientation of every instance's world-to-object map, float32 [n] of +1 or -1 (-1: a mirror), computed on the
@@ -1557,14 +1424,7 @@ class InstanceSet:
         lib = N.load_instance_near()
         return _first_k(self._handle, (lib.shray_near_triangles_instances_device, lib.shray_near_triangles_instances,
                                        lib.shray_near_triangles_instances_counters),
-                        near_params(max_near), max_near, "max_near", points, "points", self._device_points, _host_points, CLOSEST_DTYPE,
-                        (8,), True, counts, counters)
-
-    def _device_points(self, points):
-        """a GPU point tensor on the set's device as a contiguous shray_point tensor (Scene._device_points's forms)"""
-        if points.device.index != self.device:
-            raise ValueError(f"points are on {points.device}, the set on cuda:{self.device}")
-        return self._scenes[0]._device_points(points)
+                        near_params(max_near), max_near, "max_near", points, self._items("points"), CLOSEST_DTYPE, (8,), True, counts, counters)
 
     def triangles_within_into(self, points_ptr: int, count: int, out_ptr: int, instances_ptr: int = 0, counts_ptr: int = 0,
                               max_near: int = 8, stream_ptr: int = 0):
@@ -1574,8 +1434,7 @@ class InstanceSet:
         and unless `counts_ptr` is 0 `count` int32 near counts there, on a HIP stream (`stream_ptr`)."""
         np_ = near_params(max_near)
         N.check(N.load_instance_near().shray_near_triangles_instances_device(
-            self._handle, C.byref(np_), C.c_void_p(points_ptr), count, C.c_void_p(out_ptr or None), C.c_void_p(instances_ptr or None),
-            C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+            self._handle, C.byref(np_), _ptr(points_ptr), count, _ptr(out_ptr), _ptr(instances_ptr), _ptr(counts_ptr), _ptr(stream_ptr)))
 
     def near_counts(self, points):
         """How many (instance, triangle) pairs lie within each world point's max_dist2 (triangles_within with max_near = 0):
@@ -1596,14 +1455,8 @@ class InstanceSet:
         lib = N.load_instance_overlap()
         return _first_k(self._handle, (lib.shray_overlap_triangles_instances_device, lib.shray_overlap_triangles_instances,
                                        lib.shray_overlap_triangles_instances_counters),
-                        _set_overlap_params(max_triangles, any_only), max_triangles, "max_triangles", boxes, "boxes", self._device_boxes,
-                        _host_boxes, np.int32, (), True, counts, counters)
-
-    def _device_boxes(self, boxes):
-        """a GPU box tensor on the set's device as a contiguous shray_box tensor (Scene._device_boxes's forms)"""
-        if boxes.device.index != self.device:
-            raise ValueError(f"boxes are on {boxes.device}, the set on cuda:{self.device}")
-        return self._scenes[0]._device_boxes(boxes)
+                        _set_overlap_params(max_triangles, any_only), max_triangles, "max_triangles", boxes, self._items("boxes"), np.int32, (),
+                        True, counts, counters)
 
     def triangles_in_boxes_into(self, boxes_ptr: int, count: int, out_ptr: int, instances_ptr: int = 0, counts_ptr: int = 0,
                                 max_triangles: int = 8, any_only: bool = False, stream_ptr: int = 0):
@@ -1613,8 +1466,7 @@ class InstanceSet:
         instance indices there, and unless `counts_ptr` is 0 `count` int32 counts there, on a HIP stream (`stream_ptr`)."""
         op = _set_overlap_params(max_triangles, any_only)
         N.check(N.load_instance_overlap().shray_overlap_triangles_instances_device(
-            self._handle, C.byref(op), C.c_void_p(boxes_ptr), count, C.c_void_p(out_ptr or None), C.c_void_p(instances_ptr or None),
-            C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+            self._handle, C.byref(op), _ptr(boxes_ptr), count, _ptr(out_ptr), _ptr(instances_ptr), _ptr(counts_ptr), _ptr(stream_ptr)))
 
     def box_counts(self, boxes):
         """How many (instance, triangle) pairs touch each world box (triangles_in_boxes with max_triangles = 0): int32 [n],
@@ -1651,14 +1503,8 @@ class InstanceSet:
         lib = N.load_instance_intersect()
         return _first_k(self._handle, (lib.shray_intersect_triangles_instances_device, lib.shray_intersect_triangles_instances,
                                        lib.shray_intersect_triangles_instances_counters),
-                        _set_intersect_params(max_triangles, any_only, skip_shared), max_triangles, "max_triangles", triangles, "triangles",
-                        self._device_triangles, _host_triangles, np.int32, (), True, counts, counters)
-
-    def _device_triangles(self, triangles):
-        """a GPU triangle tensor on the set's device as a contiguous shray_triangle tensor (Scene._device_triangles's forms)"""
-        if triangles.device.index != self.device:
-            raise ValueError(f"triangles are on {triangles.device}, the set on cuda:{self.device}")
-        return self._scenes[0]._device_triangles(triangles)
+                        _set_intersect_params(max_triangles, any_only, skip_shared), max_triangles, "max_triangles", triangles,
+                        self._items("triangles"), np.int32, (), True, counts, counters)
 
     def intersecting_triangles_into(self, triangles_ptr: int, count: int, out_ptr: int, instances_ptr: int = 0, counts_ptr: int = 0,
                                     max_triangles: int = 8, any_only: bool = False, skip_shared: bool = False, stream_ptr: int = 0):
@@ -1669,8 +1515,7 @@ class InstanceSet:
         (`stream_ptr`)."""
         op = _set_intersect_params(max_triangles, any_only, skip_shared)
         N.check(N.load_instance_intersect().shray_intersect_triangles_instances_device(
-            self._handle, C.byref(op), C.c_void_p(triangles_ptr), count, C.c_void_p(out_ptr or None), C.c_void_p(instances_ptr or None),
-            C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+            self._handle, C.byref(op), _ptr(triangles_ptr), count, _ptr(out_ptr), _ptr(instances_ptr), _ptr(counts_ptr), _ptr(stream_ptr)))
 
     def intersection_counts(self, triangles, skip_shared: bool = False):
         """How many (instance, triangle) pairs each world query triangle intersects (intersecting_triangles with max_triangles
@@ -1688,6 +1533,10 @@ class InstanceSet:
             raise ValueError(f"instance {instance} is not among the set's {self.count}")
         return self._scenes[instance].triangle_count()
 
+    def _triangles_of(self, instance: int) -> int:
+        """triangle_count, 0 for an instance that is not among the set's (the library refuses it)"""
+        return self.triangle_count(instance) if 0 <= instance < self.count else 0
+
     def instance_intersections(self, instance: int, max_triangles: int = 8, counts: bool = True, any_only: bool = False,
                                skip_shared: bool = False, skip_own: bool = True, first: int = 0, count: int | None = None,
                                device: bool = False):
@@ -1699,29 +1548,11 @@ class InstanceSet:
         (SHRAY_INTERSECT_SKIP_OWN_INSTANCE): no pair of instance `instance` itself is a member -- by its index, so a duplicate
         instance at the same place is found.  max_triangles = 0 returns None for the indices and instances, counts=False None
         for the counts; any_only and skip_shared as for intersecting_triangles."""
-        if max_triangles == 0 and not counts:
-            raise ValueError("nothing is asked for: max_triangles is 0 and counts is False")
-        triangles = self.triangle_count(instance) if 0 <= instance < self.count else 0   # (the library refuses another instance)
-        if count is None:
-            count = max(triangles - first, 0)
-        op = _set_intersect_params(max_triangles, any_only, skip_shared, skip_own)
         lib = N.load_instance_intersect()
-        rows = count if first >= 0 and 0 <= count <= triangles - first else 0   # (the library refuses any other range)
-        if device:
-            import torch
-            where = torch.device("cuda", self.device)
-            # (an empty tensor has no pointer: one row is allocated for an empty range)
-            new = lambda want, *shape: torch.empty((max(rows, 1), *shape), dtype=torch.int32, device=where) if want else None
-            outs = (new(max_triangles > 0, max_triangles), new(max_triangles > 0, max_triangles), new(counts))
-            N.check(lib.shray_intersect_instance_device(self._handle, C.byref(op), instance, first, count,
-                                                        *(C.c_void_p(o.data_ptr() if o is not None else None) for o in outs),
-                                                        C.c_void_p(torch.cuda.current_stream(where).cuda_stream)))
-            return tuple(None if o is None else o[:rows] for o in outs)
-        new = lambda want, *shape: np.empty((rows, *shape), np.int32) if want else None
-        out, inst, n = new(max_triangles > 0, max_triangles), new(max_triangles > 0, max_triangles), new(counts)
-        N.check(lib.shray_intersect_instance(self._handle, C.byref(op), instance, first, count,
-                                             *(o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (out, inst, n))))
-        return out, inst, n
+        return _own_triangles(self._handle, (lib.shray_intersect_instance_device, lib.shray_intersect_instance),
+                              _set_intersect_params(max_triangles, any_only, skip_shared, skip_own), instance, first, count,
+                              lambda: self._triangles_of(instance), max_triangles, "max_triangles", np.int32, (), counts, device,
+                              lambda: self.device)
 
     def instance_intersections_into(self, instance: int, first: int, count: int, out_ptr: int, instances_ptr: int = 0,
                                     counts_ptr: int = 0, max_triangles: int = 8, any_only: bool = False, skip_shared: bool = False,
@@ -1732,8 +1563,7 @@ class InstanceSet:
         memory of the set's device, on a HIP stream (`stream_ptr`)."""
         op = _set_intersect_params(max_triangles, any_only, skip_shared, skip_own)
         N.check(N.load_instance_intersect().shray_intersect_instance_device(
-            self._handle, C.byref(op), instance, first, count, C.c_void_p(out_ptr or None), C.c_void_p(instances_ptr or None),
-            C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+            self._handle, C.byref(op), instance, first, count, _ptr(out_ptr), _ptr(instances_ptr), _ptr(counts_ptr), _ptr(stream_ptr)))
 
     def instances_colliding(self) -> np.ndarray:
         """bool [n]: instance i has a triangle that intersects a triangle of another instance (one SHRAY_INTERSECT_ANY |
@@ -1811,7 +1641,7 @@ class InstanceSet:
             row_count = max(self.count - first_row, 0)
         op = _pairs_params(first_row, row_count, any_only, upper, skip_shared)
         N.check(N.load_instance_pairs().shray_instance_pairs_intersect_device(
-            self._handle, C.byref(op), C.c_void_p(first_ptr or None), C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+            self._handle, C.byref(op), _ptr(first_ptr), _ptr(counts_ptr), _ptr(stream_ptr)))
 
     def colliding_pairs(self, upper: bool = True) -> np.ndarray:
         """int32 [m, 2]: the set cells (a, b) of collision_matrix in row-major order; with upper=True (the default) every
@@ -1835,8 +1665,8 @@ class InstanceSet:
         lib = N.load_instance_clearance()
         return _first_k(self._handle, (lib.shray_clearance_triangles_instances_device, lib.shray_clearance_triangles_instances,
                                        lib.shray_clearance_triangles_instances_counters),
-                        _set_clearance_params(max_pairs, max_dist2, any_only, skip_shared), max_pairs, "max_pairs", triangles, "triangles",
-                        self._device_triangles, _host_triangles, PAIR_DISTANCE_DTYPE, (12,), True, counts, counters)
+                        _set_clearance_params(max_pairs, max_dist2, any_only, skip_shared), max_pairs, "max_pairs", triangles,
+                        self._items("triangles"), PAIR_DISTANCE_DTYPE, (12,), True, counts, counters)
 
     def triangle_distances_into(self, triangles_ptr: int, count: int, out_ptr: int, instances_ptr: int = 0, counts_ptr: int = 0,
                                 max_dist2: float = float("inf"), max_pairs: int = 1, any_only: bool = False, skip_shared: bool = False,
@@ -1847,8 +1677,7 @@ class InstanceSet:
         instance indices there, and unless `counts_ptr` is 0 `count` int32 counts there, on a HIP stream (`stream_ptr`)."""
         op = _set_clearance_params(max_pairs, max_dist2, any_only, skip_shared)
         N.check(N.load_instance_clearance().shray_clearance_triangles_instances_device(
-            self._handle, C.byref(op), C.c_void_p(triangles_ptr), count, C.c_void_p(out_ptr or None), C.c_void_p(instances_ptr or None),
-            C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+            self._handle, C.byref(op), _ptr(triangles_ptr), count, _ptr(out_ptr), _ptr(instances_ptr), _ptr(counts_ptr), _ptr(stream_ptr)))
 
     def clearance_counts(self, triangles, max_dist2: float, skip_shared: bool = False):
         """How many (instance, triangle) pairs lie within `max_dist2` of each world query triangle (triangle_distances with
@@ -1871,29 +1700,11 @@ class InstanceSet:
         defaults to True here (SHRAY_CLEARANCE_SKIP_OWN_INSTANCE): no pair of instance `instance` itself is a member -- by its
         index, so a duplicate instance at the same place is found at distance 0.  max_pairs = 0 returns None for the records
         and instances, counts=False None for the counts; any_only and skip_shared as for triangle_distances."""
-        if max_pairs == 0 and not counts:
-            raise ValueError("nothing is asked for: max_pairs is 0 and counts is False")
-        triangles = self.triangle_count(instance) if 0 <= instance < self.count else 0   # (the library refuses another instance)
-        if count is None:
-            count = max(triangles - first, 0)
-        op = _set_clearance_params(max_pairs, max_dist2, any_only, skip_shared, skip_own)
         lib = N.load_instance_clearance()
-        rows = count if first >= 0 and 0 <= count <= triangles - first else 0   # (the library refuses any other range)
-        if device:
-            import torch
-            where = torch.device("cuda", self.device)
-            # (an empty tensor has no pointer: one row is allocated for an empty range)
-            new = lambda want, *shape: torch.empty((max(rows, 1), *shape), dtype=torch.int32, device=where) if want else None
-            outs = (new(max_pairs > 0, max_pairs, 12), new(max_pairs > 0, max_pairs), new(counts))
-            N.check(lib.shray_clearance_instance_device(self._handle, C.byref(op), instance, first, count,
-                                                        *(C.c_void_p(o.data_ptr() if o is not None else None) for o in outs),
-                                                        C.c_void_p(torch.cuda.current_stream(where).cuda_stream)))
-            return tuple(None if o is None else o[:rows] for o in outs)
-        new = lambda want, dtype, *shape: np.empty((rows, *shape), dtype) if want else None
-        out, inst, n = new(max_pairs > 0, PAIR_DISTANCE_DTYPE, max_pairs), new(max_pairs > 0, np.int32, max_pairs), new(counts, np.int32)
-        N.check(lib.shray_clearance_instance(self._handle, C.byref(op), instance, first, count,
-                                             *(o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (out, inst, n))))
-        return out, inst, n
+        return _own_triangles(self._handle, (lib.shray_clearance_instance_device, lib.shray_clearance_instance),
+                              _set_clearance_params(max_pairs, max_dist2, any_only, skip_shared, skip_own), instance, first, count,
+                              lambda: self._triangles_of(instance), max_pairs, "max_pairs", PAIR_DISTANCE_DTYPE, (12,), counts, device,
+                              lambda: self.device)
 
     def instance_clearance_into(self, instance: int, first: int, count: int, out_ptr: int, instances_ptr: int = 0, counts_ptr: int = 0,
                                 max_dist2: float = float("inf"), max_pairs: int = 1, any_only: bool = False, skip_shared: bool = False,
@@ -1904,8 +1715,7 @@ class InstanceSet:
         device memory of the set's device, on a HIP stream (`stream_ptr`)."""
         op = _set_clearance_params(max_pairs, max_dist2, any_only, skip_shared, skip_own)
         N.check(N.load_instance_clearance().shray_clearance_instance_device(
-            self._handle, C.byref(op), instance, first, count, C.c_void_p(out_ptr or None), C.c_void_p(instances_ptr or None),
-            C.c_void_p(counts_ptr or None), C.c_void_p(stream_ptr)))
+            self._handle, C.byref(op), instance, first, count, _ptr(out_ptr), _ptr(instances_ptr), _ptr(counts_ptr), _ptr(stream_ptr)))
 
     def instances_within(self, max_dist2: float) -> np.ndarray:
         """bool [n]: instance i has a triangle within `max_dist2` of a triangle of another instance (one SHRAY_CLEARANCE_ANY |
