@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Registers / scratch / occupancy of every kernel instance of one translation unit, from the compiler's own
-remarks (no GPU needed):   python profiles/kernel_resources.py [kernel_stack] [extra -D flags ...]"""
+remarks (no GPU needed):   python profiles/kernel_resources.py [kernel_stack] [extra -D flags ...]
+A unit outside csrc/ is named by its path, with its library's include flags after it:
+    python profiles/kernel_resources.py shader-ray_amd/near/near.hip -Ishader-ray_amd/point"""
 import os
 import re
 import subprocess
@@ -11,9 +13,10 @@ PKG = os.path.join(ROOT, "shader-ray_amd")
 
 
 def resources(unit="kernel_stack", extra=()):
+    source = unit if unit.endswith(".hip") else f"{PKG}/csrc/{unit}.hip"
     cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
            "-fno-slp-vectorize", "-fhip-fp32-correctly-rounded-divide-sqrt", f"-I{ROOT}/include", f"-I{PKG}/csrc", *extra,
-           "-Rpass-analysis=kernel-resource-usage", "-c", f"{PKG}/csrc/{unit}.hip", "-o", "/dev/null"]
+           "-Rpass-analysis=kernel-resource-usage", "-c", source, "-o", "/dev/null"]
     text = subprocess.run(cmd, capture_output=True, text=True).stderr
     rows, cur = [], {}
     for line in text.splitlines():
@@ -31,7 +34,7 @@ def resources(unit="kernel_stack", extra=()):
     except FileNotFoundError:
         names = [r["name"] for r in rows]
     for r, n in zip(rows, names):
-        r["pretty"] = re.sub(r"\(.*", "", n.replace("shray::", "").replace("void ", ""))
+        r["pretty"] = re.sub(r"\(.*", "", n.replace("shray::", "").replace("(anonymous namespace)::", "").replace("void ", ""))
     return rows
 
 

@@ -82,7 +82,20 @@ def test_mixed_children():
         assert found == expected, name
 
 
-@pytest.mark.parametrize("name", T.NAMES)
+def test_spine3_is_the_spine_the_walks_are_tested_on():
+    """7 nodes, one branch at each of the heights 1 to 3; the root's branch child is its negative one, that branch's branch
+    child its positive one, and the deepest branch holds two leaves: four leaves of 1, 2, 3 and 1 triangles"""
+    tree, _ = shape("spine3")
+    h = T.heights(tree)
+    assert tree.node_count == 7 and list(T.height_profile(tree)) == [4, 1, 1, 1] and h[0] == 3
+    n1 = tree.negative[0]
+    assert h[n1] == 2 and h[tree.positive[0]] == 0
+    n2 = tree.positive[n1]
+    assert h[n2] == 1 and h[tree.negative[n1]] == 0 and h[tree.negative[n2]] == h[tree.positive[n2]] == 0
+    assert tree.triangles[tree.negative < 0].tolist() == [1, 2, 3, 1] and "spine3" not in T.NAMES
+
+
+@pytest.mark.parametrize("name", T.NAMES + tuple(T.WALK_SHAPES))
 def test_the_arrays_are_a_valid_preorder_bvh(name):
     tree, vd = shape(name)
     n = tree.node_count

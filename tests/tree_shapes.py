@@ -78,6 +78,14 @@ SHAPES = {
 }
 NAMES = tuple(SHAPES)
 
+# Shapes for the walks alone (test_gpu_packed_walk.py), outside NAMES: the schedule's tests do not run over them.
+#   spine3   a spine of height 3 that leans to the negative side once and to the positive side once: root { N1, leaf },
+#            N1 { leaf, N2 }, N2 { leaf, leaf } -- 7 nodes; a walk down it holds two stack entries at once, and a pop can
+#            return a branch whose own sibling still waits
+WALK_SHAPES = {
+    "spine3": lambda: B(B(LEAF, B(LEAF, LEAF)), LEAF),
+}
+
 # name -> (nodes, branches per height from 1 up): what the module's table claims
 PROFILES = {
     "leaf_root": (1, []),
@@ -124,7 +132,8 @@ def height_profile(tree) -> np.ndarray:
 
 
 def build(name):
-    parent, negative, positive = _preorder(SHAPES[name]())
+    every = {**SHAPES, **WALK_SHAPES}
+    parent, negative, positive = _preorder(every[name]())
     n = len(parent)
     leaf = np.nonzero(negative < 0)[0]                       # in pre-order: from lower x to higher
     count = 1 + np.arange(len(leaf)) % 3 if n > 1 else np.array([3])
@@ -132,7 +141,7 @@ def build(name):
     start[leaf], triangles[leaf] = np.cumsum(count) - count, count
     T = int(count.sum())
 
-    rng = np.random.default_rng(1000 + NAMES.index(name))
+    rng = np.random.default_rng(1000 + tuple(every).index(name))
     corners = np.empty((T, 3, 3), np.float64)
     x0 = 1.0 + PITCH * np.arange(T)
     corners[:, :, 0] = x0[:, None] + WIDTH * np.array([0.0, 1.0, 0.5]) * (0.6 + 0.4 * rng.random((T, 3)))
