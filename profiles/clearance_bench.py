@@ -20,17 +20,13 @@ blocking counting run over 2^10 of the same queries; the rows with +inf have non
                 the times and whether every dist2 and triangle agrees
 
 Usage: python profiles/clearance_bench.py [--trials 15] [--warmup 5]"""
-import argparse
 import ctypes as C
-import json
-import os
 import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
+import bench_harness as H
 
 F = np.float32
 COUNT = 1 << 18
@@ -38,42 +34,21 @@ SAMPLE = 1 << 10
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--trials", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=5)
-    args = ap.parse_args()
+    args = H.parser().parse_args()
     import torch
-    from __graft_entry__ import load_package
     import clearance_ref as CR
     import intersect_cases as IC
     import intersect_ref as IR
     import point_query_ref as PQ
 
-    pkg = load_package()
+    pkg = H.load_package()
     N = pkg._native
     lib = N.load_clearance()
     stream = torch.cuda.current_stream()
+    median_ms = H.median_timer(args, slow_ms=500.0)
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        fn()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b)
-
-    def median_ms(fn):
-        trials, warmup = args.trials, args.warmup
-        if timed(fn) > 500.0:
-            trials, warmup = 3, 0
-        for _ in range(warmup):
-            fn()
-        times = [timed(fn) for _ in range(trials)]
-        return float(np.median(times)), float(min(times)), float(max(times)), trials
-
-    def entry(queries, ms, lo, hi, trials):
-        return {"queries": queries, "ms": round(ms, 4), "ms_min_max": [round(lo, 4), round(hi, 4)], "trials": trials,
-                "Mqueries_s": round(queries / ms / 1e3, 4)}
+    def entry(queries, t):
+        return H.entry(t, "Mqueries_s", queries, queries=queries)
 
     def launcher(scene, d_queries, count, k, md, counts, any_only, skip, d_out, d_cnt):
         """the item form on d_queries, or with d_queries None the self form over the first `count` triangles"""
@@ -91,7 +66,7 @@ def main():
     def row(scene, sample, d_queries, count, k, md, counts, any_only, skip):
         d_out = torch.empty((count, max(k, 1), 12), dtype=torch.int32, device="cuda")
         d_cnt = torch.empty(count, dtype=torch.int32, device="cuda")
-        r = entry(count, *median_ms(launcher(scene, d_queries, count, k, md, counts, any_only, skip, d_out, d_cnt)))
+        r = entry(count, median_ms(launcher(scene, d_queries, count, k, md, counts, any_only, skip, d_out, d_cnt)))
         r["max_dist2"] = float(md)
         if k:
             d2 = d_out[:, 0, 3].contiguous().view(torch.float32)
@@ -108,53 +83,48 @@ def main():
         return r
 
     out = {"trials": args.trials, "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
-    world = pkg.World(pkg.scenes.bunny_trisrc())
-    pos = np.asarray(world.arrays()["vertex_positions"], F)
-    scene = pkg.Scene(world.flatten())
-    tris = pos.reshape(-1, 3, 3)
-    T = len(tris)
-    diagonal = IC.scene_extent(pos)
-    rng = np.random.default_rng(3)
-    base = tris[rng.integers(0, T, COUNT)].astype(np.float64)
-    centre = base.mean(1, keepdims=True)
-    way = rng.normal(size=(COUNT, 1, 3))
-    way /= np.linalg.norm(way, axis=2, keepdims=True)
-    near = (centre + (base - centre) * 0.8 + way * diagonal * 0.01 * rng.random((COUNT, 1, 1))).astype(F)
-    far = (centre + (base - centre) * 0.8 + way * diagonal * (2 + 8 * rng.random((COUNT, 1, 1)))).astype(F)
-    dev = lambda q: torch.from_numpy(IR.make_triangles(q).view(F).reshape(-1, 12).copy()).cuda()
-    d_near, d_far = dev(near), dev(far)
-    inf, tol, thin = F(np.inf), F((0.02 * diagonal) ** 2), F((0.005 * diagonal) ** 2)
-    pick = np.sort(np.random.default_rng(5).permutation(T)[:SAMPLE])
-    res = {"triangles": T, "diagonal": round(diagonal, 4)}
-    res["near_K1"] = row(scene, near[:SAMPLE], d_near, COUNT, 1, inf, False, False, False)
-    res["near_K8_tol"] = row(scene, near[:SAMPLE], d_near, COUNT, 8, tol, True, False, False)
-    res["near_any_tol"] = row(scene, near[:SAMPLE], d_near, COUNT, 0, tol, True, True, False)
-    res["far_K1"] = row(scene, far[:SAMPLE], d_far, COUNT, 1, inf, False, False, False)
-    res["far_any_tol"] = row(scene, far[:SAMPLE], d_far, COUNT, 0, tol, True, True, False)
-    res["self_K1_skip"] = row(scene, tris[pick], None, T, 1, inf, False, False, True)
-    res["self_any_skip_tol"] = row(scene, tris[pick], None, T, 0, thin, True, True, True)
-    out["bunny"] = res
+    with H.bunny_scene(pkg) as (world, scene, pos):
+        tris = pos.reshape(-1, 3, 3)
+        T = len(tris)
+        diagonal = IC.scene_extent(pos)
+        rng = np.random.default_rng(3)
+        base = tris[rng.integers(0, T, COUNT)].astype(np.float64)
+        centre = base.mean(1, keepdims=True)
+        way = rng.normal(size=(COUNT, 1, 3))
+        way /= np.linalg.norm(way, axis=2, keepdims=True)
+        near = (centre + (base - centre) * 0.8 + way * diagonal * 0.01 * rng.random((COUNT, 1, 1))).astype(F)
+        far = (centre + (base - centre) * 0.8 + way * diagonal * (2 + 8 * rng.random((COUNT, 1, 1)))).astype(F)
+        d_near, d_far = H.upload(IR.make_triangles(near), 12), H.upload(IR.make_triangles(far), 12)
+        inf, tol, thin = F(np.inf), F((0.02 * diagonal) ** 2), F((0.005 * diagonal) ** 2)
+        pick = np.sort(np.random.default_rng(5).permutation(T)[:SAMPLE])
+        res = {"triangles": T, "diagonal": round(diagonal, 4)}
+        res["near_K1"] = row(scene, near[:SAMPLE], d_near, COUNT, 1, inf, False, False, False)
+        res["near_K8_tol"] = row(scene, near[:SAMPLE], d_near, COUNT, 8, tol, True, False, False)
+        res["near_any_tol"] = row(scene, near[:SAMPLE], d_near, COUNT, 0, tol, True, True, False)
+        res["far_K1"] = row(scene, far[:SAMPLE], d_far, COUNT, 1, inf, False, False, False)
+        res["far_any_tol"] = row(scene, far[:SAMPLE], d_far, COUNT, 0, tol, True, True, False)
+        res["self_K1_skip"] = row(scene, tris[pick], None, T, 1, inf, False, False, True)
+        res["self_any_skip_tol"] = row(scene, tris[pick], None, T, 0, thin, True, True, True)
+        out["bunny"] = res
 
-    # what a caller would write today: every query against every triangle, the restatement on torch tensors
-    few = near[:SAMPLE]
-    d_few = d_near[:SAMPLE].contiguous()
-    d_out = torch.empty((SAMPLE, 1, 12), dtype=torch.int32, device="cuda")
-    d_cnt = torch.empty(SAMPLE, dtype=torch.int32, device="cuda")
-    ours = entry(SAMPLE, *median_ms(launcher(scene, d_few, SAMPLE, 1, inf, False, False, False, d_out, d_cnt)))
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    d2, _ = CR.pair_table(PQ.TorchOps("cuda"), few, pos, pairs=1 << 22)
-    torch.cuda.synchronize()
-    brute_ms = (time.perf_counter() - t0) * 1e3
-    got = d_out.cpu().numpy()
-    nearest = d2.argmin(1)   # (the first of equal minima: the lowest index)
-    agree = bool(np.array_equal(got[:, 0, 3].view(F).view(np.uint32), d2[np.arange(SAMPLE), nearest].view(np.uint32)) and
-                 np.array_equal(got[:, 0, 7], nearest.astype(np.int32)))
-    out["torch_vs_K1"] = {"kernel": ours, "torch_ms": round(brute_ms, 1), "torch_over_kernel": round(brute_ms / ours["ms"], 1),
-                          "dist2_and_triangle_agree": agree}
-    scene.close()
-    world.close()
-    print(json.dumps(out))
+        # what a caller would write today: every query against every triangle, the restatement on torch tensors
+        few = near[:SAMPLE]
+        d_few = d_near[:SAMPLE].contiguous()
+        d_out = torch.empty((SAMPLE, 1, 12), dtype=torch.int32, device="cuda")
+        d_cnt = torch.empty(SAMPLE, dtype=torch.int32, device="cuda")
+        ours = entry(SAMPLE, median_ms(launcher(scene, d_few, SAMPLE, 1, inf, False, False, False, d_out, d_cnt)))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        d2, _ = CR.pair_table(PQ.TorchOps("cuda"), few, pos, pairs=1 << 22)
+        torch.cuda.synchronize()
+        brute_ms = (time.perf_counter() - t0) * 1e3
+        got = d_out.cpu().numpy()
+        nearest = d2.argmin(1)   # (the first of equal minima: the lowest index)
+        agree = bool(np.array_equal(got[:, 0, 3].view(F).view(np.uint32), d2[np.arange(SAMPLE), nearest].view(np.uint32)) and
+                     np.array_equal(got[:, 0, 7], nearest.astype(np.int32)))
+        out["torch_vs_K1"] = {"kernel": ours, "torch_ms": round(brute_ms, 1), "torch_over_kernel": round(brute_ms / ours["ms"], 1),
+                              "dist2_and_triangle_agree": agree}
+    H.emit(out, args)
 
 
 if __name__ == "__main__":

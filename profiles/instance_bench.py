@@ -9,97 +9,50 @@
 
 Every query time is the median of --trials launches after --warmup launches, bracketed by HIP events on the current torch stream.
 Usage: python profiles/instance_bench.py [--trials 15] [--warmup 5] [--skip-merged]"""
-import argparse
-import json
 import os
-import sys
 import tempfile
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
+import bench_harness as H
+from bench_workloads import ao_rays, camera_rays, down_rays, grid_transforms
 
 F = np.float32
 
 
-def rotation(rng):
-    q = rng.normal(size=4)
-    q /= np.linalg.norm(q)
-    w, x, y, z = q
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
-                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
-
-
-def grid_transforms(dims, spacing, rng, scale=(0.6, 1.0)):
-    cells = np.stack(np.meshgrid(*[np.arange(k) for k in dims], indexing="ij"), -1).reshape(-1, len(dims))
-    M = np.zeros((len(cells), 3, 4))
-    for i, c in enumerate(cells):
-        M[i, :, :3] = rotation(rng) * rng.uniform(*scale)
-        M[i, :len(c), 3] = c * spacing
-    return M.astype(F)
-
-
-def down_rays(lo, hi, n, rng):
-    """rays from above the region's top, aimed at random points of its floor (a camera looking down at the grid)"""
-    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
-    size = hi - lo
-    o = lo + size * rng.random((n, 3))
-    o[:, 2] = hi[2] + size.max()
-    aim = lo + size * rng.random((n, 3))
-    aim[:, 2] = lo[2]
-    d = aim - o
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    return o.astype(F), d.astype(F)
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--trials", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = H.parser()
     ap.add_argument("--skip-merged", action="store_true", help="(b) without the merged 4.4M-triangle scene")
     args = ap.parse_args()
     import torch
     import bench
     import ray_query_ref as R
-    from ray_query_bench import ao_rays, camera_rays
-    from __graft_entry__ import load_package
 
-    pkg = load_package()
+    pkg = H.load_package()
     rng = np.random.default_rng(2026)
     stream = torch.cuda.current_stream()
 
-    def median_ms(fn):
-        for _ in range(args.warmup):
-            fn()
-        times = []
-        for _ in range(args.trials):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            fn()
-            b.record(stream)
-            b.synchronize()
-            times.append(a.elapsed_time(b))
-        return round(float(np.median(times)), 4)
+    timing = H.median_timer(args)
+
+    def median_of(fn):
+        return round(timing(fn).ms, 4)
 
     def device_rays(o, d, tmax):
-        rays = pkg.tracer.make_rays(o, d, tmax)
-        return torch.from_numpy(rays.view(np.float32).reshape(-1, 8).copy()).cuda()
+        return H.upload(pkg.tracer.make_rays(o, d, tmax), 8)
 
     def time_set(s, d_rays):
         n = d_rays.shape[0]
         hits = torch.empty((n, 4), dtype=torch.int32, device="cuda")
         inst = torch.empty(n, dtype=torch.int32, device="cuda")
-        ms = median_ms(lambda: s.trace_rays_into(d_rays.data_ptr(), n, hits.data_ptr(), inst.data_ptr(), stream.cuda_stream))
+        ms = median_of(lambda: s.trace_rays_into(d_rays.data_ptr(), n, hits.data_ptr(), inst.data_ptr(), stream.cuda_stream))
         torch.cuda.synchronize()
         return {"rays": n, "ms": ms, "Mrays_s": round(n / ms / 1e3, 1), "hit_fraction": round(float((hits[:, 3] >= 0).float().mean()), 4)}
 
     def time_scene(sc, d_rays):
         n = d_rays.shape[0]
         hits = torch.empty((n, 4), dtype=torch.int32, device="cuda")
-        ms = median_ms(lambda: sc.trace_rays_into(d_rays.data_ptr(), n, hits.data_ptr(), stream.cuda_stream))
+        ms = median_of(lambda: sc.trace_rays_into(d_rays.data_ptr(), n, hits.data_ptr(), stream.cuda_stream))
         torch.cuda.synchronize()
         return {"rays": n, "ms": ms, "Mrays_s": round(n / ms / 1e3, 1), "hit_fraction": round(float((hits[:, 3] >= 0).float().mean()), 4)}
 
@@ -107,12 +60,12 @@ def main():
 
     # (a) -----------------------------------------------------------------------------------------------------------------
     world = pkg.World(pkg.scenes.bunny_trisrc())
-    W, H = 1920, 1080
-    params = bench.orbit_params(pkg, world, W, H)[0]
+    W, HEIGHT = 1920, 1080
+    params = bench.orbit_params(pkg, world, W, HEIGHT)[0]
     bunny = pkg.Scene(world.flatten())
     one = pkg.tracer.InstanceSet([bunny], np.eye(3, 4, dtype=F)[None])
     positions = np.asarray(world.arrays()["vertex_positions"], F)
-    o, d = camera_rays(params, W, H, R.xform)
+    o, d = camera_rays(params, W, HEIGHT, R.xform)
     primary = device_rays(o, d, F(1e7))
     o, d, tmax = ao_rays(positions, 1 << 21, seed=2024)
     ao = device_rays(o, d, tmax)
@@ -160,7 +113,7 @@ def main():
     del grid_rays
 
     # (c) -----------------------------------------------------------------------------------------------------------------
-    lobed_world = pkg.World(os.path.join(ROOT, "tests", "golden", "lobed_528.trisrc"))
+    lobed_world = pkg.World(os.path.join(H.ROOT, "tests", "golden", "lobed_528.trisrc"))
     lobed = pkg.Scene(lobed_world.flatten())
     lp = np.asarray(lobed_world.arrays()["vertex_positions"], F).reshape(-1, 3)
     size = float(np.ptp(lp, axis=0).max())
@@ -185,7 +138,7 @@ def main():
         d_out[str(n)] = {"update_ms_median": round(1e3 * float(np.median(times)), 2), "update_ms_min": round(1e3 * min(times), 2)}
         s.close()
     out["d_update"] = d_out
-    print(json.dumps(out))
+    H.emit(out, args)
 
 
 if __name__ == "__main__":

@@ -25,63 +25,41 @@ bounds evaluated, leaf visits, triangle tests, instance walks begun) come from o
 queries.
 
 Usage: python profiles/instance_clearance_bench.py [--trials 15] [--warmup 5] [--queries 262144] [--out FILE]"""
-import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
+import bench_harness as H
+from bench_workloads import grid_transforms
 
 F = np.float32
 SAMPLE = 1 << 10
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--trials", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = H.parser(out=os.path.join(H.ROOT, "profiles", "instance_clearance_bench.json"))
     ap.add_argument("--queries", type=int, default=1 << 18)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "instance_clearance_bench.json"))
     args = ap.parse_args()
     import torch
-    from __graft_entry__ import load_package
-    from instance_bench import grid_transforms
     import intersect_cases as IC
     import intersect_ref as IR
 
-    pkg = load_package()
+    pkg = H.load_package()
     stream = torch.cuda.current_stream()
     n = args.queries
+    median_ms = H.median_timer(args, slow_ms=500.0)
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        fn()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b)
+    def time_cell(fn, count):
+        return H.entry(median_ms(fn), "Mqueries_s", count, queries=count)
 
-    def median_ms(fn, count):
-        trials, warmup = args.trials, args.warmup
-        if timed(fn) > 500.0:
-            trials, warmup = 3, 0
-        for _ in range(warmup):
-            fn()
-        times = [timed(fn) for _ in range(trials)]
-        ms = float(np.median(times))
-        return {"queries": count, "ms": round(ms, 4), "ms_min_max": [round(min(times), 4), round(max(times), 4)], "trials": trials,
-                "Mqueries_s": round(count / ms / 1e3, 4)}
-
-    dev = lambda q: torch.from_numpy(IR.make_triangles(q).view(F).reshape(-1, 12).copy()).cuda()
+    dev = lambda q: H.upload(IR.make_triangles(q), 12)   # noqa: E731
 
     def item_row(s, plain, queries, d_queries, k, md, counts, any_only, what):
         d_out = torch.empty((n, max(k, 1), 12), dtype=torch.int32, device="cuda")
         d_inst = torch.empty((n, max(k, 1)), dtype=torch.int32, device="cuda")
         d_cnt = torch.empty(n, dtype=torch.int32, device="cuda")
-        r = median_ms(lambda: s.triangle_distances_into(d_queries.data_ptr(), n, d_out.data_ptr() if k else 0, d_inst.data_ptr() if k else 0,
+        r = time_cell(lambda: s.triangle_distances_into(d_queries.data_ptr(), n, d_out.data_ptr() if k else 0, d_inst.data_ptr() if k else 0,
                                                         d_cnt.data_ptr() if counts else 0, md, k, any_only, False, stream.cuda_stream), n)
         r["max_dist2"] = float(md)
         if counts:
@@ -93,7 +71,7 @@ def main():
         if plain is not None:
             d_plain = torch.empty((n, max(k, 1), 12), dtype=torch.int32, device="cuda")
             d_plain_cnt = torch.empty(n, dtype=torch.int32, device="cuda")
-            p = median_ms(lambda: plain.triangle_distances_into(d_queries.data_ptr(), n, d_plain.data_ptr() if k else 0,
+            p = time_cell(lambda: plain.triangle_distances_into(d_queries.data_ptr(), n, d_plain.data_ptr() if k else 0,
                                                                 d_plain_cnt.data_ptr() if counts else 0, md, k, any_only, False,
                                                                 stream.cuda_stream), n)
             same = (not k or bool(torch.equal(d_out, d_plain))) and (not counts or bool(torch.equal(d_cnt, d_plain_cnt)))
@@ -105,7 +83,7 @@ def main():
         d_out = torch.empty((triangles, max(k, 1), 12), dtype=torch.int32, device="cuda")
         d_inst = torch.empty((triangles, max(k, 1)), dtype=torch.int32, device="cuda")
         d_cnt = torch.empty(triangles, dtype=torch.int32, device="cuda")
-        r = median_ms(lambda: s.instance_clearance_into(instance, 0, triangles, d_out.data_ptr() if k else 0, d_inst.data_ptr() if k else 0,
+        r = time_cell(lambda: s.instance_clearance_into(instance, 0, triangles, d_out.data_ptr() if k else 0, d_inst.data_ptr() if k else 0,
                                                         d_cnt.data_ptr() if counts else 0, md, k, any_only, skip_shared, skip_own,
                                                         stream.cuda_stream), triangles)
         r["max_dist2"] = float(md)
@@ -119,7 +97,7 @@ def main():
         if plain is not None:
             d_plain = torch.empty((triangles, max(k, 1), 12), dtype=torch.int32, device="cuda")
             d_plain_cnt = torch.empty(triangles, dtype=torch.int32, device="cuda")
-            p = median_ms(lambda: plain.self_clearance_into(0, triangles, d_plain.data_ptr() if k else 0, d_plain_cnt.data_ptr() if counts else 0,
+            p = time_cell(lambda: plain.self_clearance_into(0, triangles, d_plain.data_ptr() if k else 0, d_plain_cnt.data_ptr() if counts else 0,
                                                             md, k, any_only, skip_shared, stream.cuda_stream), triangles)
             same = (not k or bool(torch.equal(d_out, d_plain))) and (not counts or bool(torch.equal(d_cnt, d_plain_cnt)))
             r = {"instance": r, "scene": p, "instance_over_scene": round(r["ms"] / p["ms"], 3), "same_bytes": same}
@@ -127,63 +105,55 @@ def main():
         return r
 
     out = {"trials": args.trials, "warmup": args.warmup, "queries": n, "device": torch.cuda.get_device_name(0)}
-    world = pkg.World(pkg.scenes.bunny_trisrc())
-    pos = np.asarray(world.arrays()["vertex_positions"], F)
-    bunny = pkg.Scene(world.flatten())
-    tris = pos.reshape(-1, 3, 3)
-    T = len(tris)
-    diagonal = IC.scene_extent(pos)
-    extent = float(np.ptp(pos.reshape(-1, 3).astype(np.float64), axis=0).max())
-    out["triangles"], out["diagonal"] = T, round(diagonal, 4)
-    inf, tol, thin = F(np.inf), F((0.02 * diagonal) ** 2), F((0.005 * diagonal) ** 2)
+    with H.bunny_scene(pkg) as (world, bunny, pos):
+        tris = pos.reshape(-1, 3, 3)
+        T = len(tris)
+        diagonal = IC.scene_extent(pos)
+        extent = float(np.ptp(pos.reshape(-1, 3).astype(np.float64), axis=0).max())
+        out["triangles"], out["diagonal"] = T, round(diagonal, 4)
+        inf, tol, thin = F(np.inf), F((0.02 * diagonal) ** 2), F((0.005 * diagonal) ** 2)
 
-    def queries_for(maps, seed):
-        """clearance_bench.py's near and far triangles, each mapped (in double, rounded) into a random instance"""
-        rng = np.random.default_rng(seed)
-        base = tris[rng.integers(0, T, n)].astype(np.float64)
-        centre = base.mean(1, keepdims=True)
-        way = rng.normal(size=(n, 1, 3))
-        way /= np.linalg.norm(way, axis=2, keepdims=True)
-        near = centre + (base - centre) * 0.8 + way * diagonal * 0.01 * rng.random((n, 1, 1))
-        far = centre + (base - centre) * 0.8 + way * diagonal * (2 + 8 * rng.random((n, 1, 1)))
-        M = np.asarray(maps, np.float64)[rng.integers(0, len(maps), n)]
-        place = lambda q: (np.einsum("nrc,nkc->nkr", M[:, :, :3], q) + M[:, None, :, 3]).astype(F)
-        return place(near), place(far)
+        def queries_for(maps, seed):
+            """clearance_bench.py's near and far triangles, each mapped (in double, rounded) into a random instance"""
+            rng = np.random.default_rng(seed)
+            base = tris[rng.integers(0, T, n)].astype(np.float64)
+            centre = base.mean(1, keepdims=True)
+            way = rng.normal(size=(n, 1, 3))
+            way /= np.linalg.norm(way, axis=2, keepdims=True)
+            near = centre + (base - centre) * 0.8 + way * diagonal * 0.01 * rng.random((n, 1, 1))
+            far = centre + (base - centre) * 0.8 + way * diagonal * (2 + 8 * rng.random((n, 1, 1)))
+            M = np.asarray(maps, np.float64)[rng.integers(0, len(maps), n)]
+            place = lambda q: (np.einsum("nrc,nkc->nkr", M[:, :, :3], q) + M[:, None, :, 3]).astype(F)
+            return place(near), place(far)
 
-    def rows(s, plain, maps, seed, what, own_instance):
-        near, far = queries_for(maps, seed)
-        d_near, d_far = dev(near), dev(far)
-        res = {}
-        res["near_K1"] = item_row(s, plain, near, d_near, 1, inf, False, False, what)
-        res["near_K8_tol"] = item_row(s, plain, near, d_near, 8, tol, True, False, what)
-        res["near_any_tol"] = item_row(s, plain, near, d_near, 0, tol, True, True, what)
-        res["far_K1"] = item_row(s, plain, far, d_far, 1, inf, False, False, what)
-        res["far_any_tol"] = item_row(s, plain, far, d_far, 0, tol, True, True, what)
-        if plain is not None:
-            res["own_K1_skip"] = own_row(s, plain, 0, T, 1, inf, False, False, True, False, what)
-            res["own_any_tol"] = own_row(s, plain, 0, T, 0, thin, True, True, True, False, what)
-        else:
-            res["own_instance"] = own_instance
-            res["own_K1_skip"] = own_row(s, None, own_instance, T, 1, inf, False, False, False, True, what)
-            res["own_any_tol"] = own_row(s, None, own_instance, T, 0, tol, True, True, False, True, what)
-        return res
+        def rows(s, plain, maps, seed, what, own_instance):
+            near, far = queries_for(maps, seed)
+            d_near, d_far = dev(near), dev(far)
+            res = {}
+            res["near_K1"] = item_row(s, plain, near, d_near, 1, inf, False, False, what)
+            res["near_K8_tol"] = item_row(s, plain, near, d_near, 8, tol, True, False, what)
+            res["near_any_tol"] = item_row(s, plain, near, d_near, 0, tol, True, True, what)
+            res["far_K1"] = item_row(s, plain, far, d_far, 1, inf, False, False, what)
+            res["far_any_tol"] = item_row(s, plain, far, d_far, 0, tol, True, True, what)
+            if plain is not None:
+                res["own_K1_skip"] = own_row(s, plain, 0, T, 1, inf, False, False, True, False, what)
+                res["own_any_tol"] = own_row(s, plain, 0, T, 0, thin, True, True, True, False, what)
+            else:
+                res["own_instance"] = own_instance
+                res["own_K1_skip"] = own_row(s, None, own_instance, T, 1, inf, False, False, False, True, what)
+                res["own_any_tol"] = own_row(s, None, own_instance, T, 0, tol, True, True, False, True, what)
+            return res
 
-    eye = np.eye(3, 4, dtype=F)[None]
-    one = pkg.tracer.InstanceSet([bunny], eye)
-    out["a_identity"] = rows(one, bunny, eye, 3, "one identity instance", 0)
-    one.close()
+        eye = np.eye(3, 4, dtype=F)[None]
+        one = pkg.tracer.InstanceSet([bunny], eye)
+        out["a_identity"] = rows(one, bunny, eye, 3, "one identity instance", 0)
+        one.close()
 
-    M = grid_transforms((8, 8), 1.5 * extent, np.random.default_rng(2026))
-    grid = pkg.tracer.InstanceSet([bunny] * 64, M)
-    out["b_bunny_8x8"] = rows(grid, None, M, 4, "64 copies", 27)
-    grid.close()
-    bunny.close()
-    world.close()
-    text = json.dumps(out)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    print(text)
+        M = grid_transforms((8, 8), 1.5 * extent, np.random.default_rng(2026))
+        grid = pkg.tracer.InstanceSet([bunny] * 64, M)
+        out["b_bunny_8x8"] = rows(grid, None, M, 4, "64 copies", 27)
+        grid.close()
+    H.emit(out, args)
 
 
 if __name__ == "__main__":

@@ -17,15 +17,12 @@ with the fastest and the slowest launch.  The walk counters per query (image-box
 walks begun) come from one blocking counting run over 2^12 of the same queries, and with them the mean count.
 
 Usage: python profiles/instance_intersect_bench.py [--trials 15] [--warmup 5] [--queries 262144] [--out FILE]"""
-import argparse
-import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
+import bench_harness as H
+from bench_workloads import grid_transforms
 
 F = np.float32
 SAMPLE = 1 << 12
@@ -34,41 +31,22 @@ TALLIES = ("node_visits", "leaf_visits", "triangle_tests", "traversals")
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--trials", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = H.parser()
     ap.add_argument("--queries", type=int, default=1 << 18)
-    ap.add_argument("--out", default=None, help="also write the JSON here")
     args = ap.parse_args()
     import torch
-    from __graft_entry__ import load_package
-    from instance_bench import grid_transforms
     import intersect_cases as TC
 
-    pkg = load_package()
+    pkg = H.load_package()
     stream = torch.cuda.current_stream()
     n = args.queries
+    median_ms = H.median_timer(args, slow_ms=1000.0)
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        fn()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b)
-
-    def median_ms(fn, items):
-        trials, warmup = args.trials, args.warmup
-        if timed(fn) > 1000.0:
-            trials, warmup = 3, 0
-        for _ in range(warmup):
-            fn()
-        times = [timed(fn) for _ in range(trials)]
-        return {"ms": round(float(np.median(times)), 4), "ms_min_max": [round(min(times), 4), round(max(times), 4)], "trials": trials,
-                "Mqueries_s": round(items / float(np.median(times)) / 1e3, 4)}
+    def time_cell(fn, items):
+        return H.entry(median_ms(fn), "Mqueries_s", items)
 
     def as_tensor(corners):
-        return torch.from_numpy(pkg.tracer.make_triangles(corners).view(F).reshape(-1, 12).copy()).cuda()
+        return H.upload(pkg.tracer.make_triangles(corners), 12)
 
     def cells(s, plain, d_q, what):
         """per form: the set's time and, with `plain` (a Scene), Scene.intersecting_triangles' on the same queries"""
@@ -83,12 +61,12 @@ def main():
         d_inst = torch.empty((n, 8), dtype=torch.int32, device="cuda")
         d_cnt = torch.empty(n, dtype=torch.int32, device="cuda")
         for name, k, any_only in FORMS:
-            r = median_ms(lambda: s.intersecting_triangles_into(d_q.data_ptr(), n, d_out.data_ptr() if k else 0, d_inst.data_ptr() if k else 0,
+            r = time_cell(lambda: s.intersecting_triangles_into(d_q.data_ptr(), n, d_out.data_ptr() if k else 0, d_inst.data_ptr() if k else 0,
                                                                 d_cnt.data_ptr(), k, any_only, False, stream.cuda_stream), n)
             if plain is not None:
                 d_plain = torch.empty((n, 8), dtype=torch.int32, device="cuda")
                 d_plain_cnt = torch.empty(n, dtype=torch.int32, device="cuda")
-                p = median_ms(lambda: plain.intersecting_triangles_into(d_q.data_ptr(), n, d_plain.data_ptr() if k else 0,
+                p = time_cell(lambda: plain.intersecting_triangles_into(d_q.data_ptr(), n, d_plain.data_ptr() if k else 0,
                                                                         d_plain_cnt.data_ptr(), k, any_only, False, stream.cuda_stream), n)
                 r = {"instance": r, "scene": p, "instance_over_scene": round(r["ms"] / p["ms"], 3),
                      "same_answer": bool(torch.equal(d_cnt, d_plain_cnt)) and (k == 0 or bool(torch.equal(d_out, d_plain)))}
@@ -115,54 +93,46 @@ def main():
 
     out = {"trials": args.trials, "warmup": args.warmup, "queries": n, "device": torch.cuda.get_device_name(0)}
     rng = np.random.default_rng(2026)
-    world = pkg.World(pkg.scenes.bunny_trisrc())
-    positions = np.asarray(world.arrays()["vertex_positions"], F)
-    verts = positions.reshape(-1, 3).astype(np.float64)
-    extent = float(np.linalg.norm(verts.max(0) - verts.min(0)))
-    bunny = pkg.Scene(world.flatten())
-    triangles = len(positions) // 9
-    out["triangles"] = triangles
+    with H.bunny_scene(pkg) as (world, bunny, positions):
+        verts = positions.reshape(-1, 3).astype(np.float64)
+        extent = float(np.linalg.norm(verts.max(0) - verts.min(0)))
+        triangles = len(positions) // 9
+        out["triangles"] = triangles
 
-    eye = np.eye(3, 4, dtype=F)[None]
-    one = pkg.tracer.InstanceSet([bunny], eye)
-    d_moved, d_slicers = queries_of(positions, eye, extent, rng)
-    out["a_identity"] = {"moved": cells(one, bunny, d_moved, "one identity instance, moved copies"),
-                         "slicers": cells(one, bunny, d_slicers, "one identity instance, slicers")}
-    one.close()
+        eye = np.eye(3, 4, dtype=F)[None]
+        one = pkg.tracer.InstanceSet([bunny], eye)
+        d_moved, d_slicers = queries_of(positions, eye, extent, rng)
+        out["a_identity"] = {"moved": cells(one, bunny, d_moved, "one identity instance, moved copies"),
+                             "slicers": cells(one, bunny, d_slicers, "one identity instance, slicers")}
+        one.close()
 
-    widest = float(np.ptp(verts, axis=0).max())
-    M = grid_transforms((8, 8), 1.5 * widest, np.random.default_rng(2026))
-    grid = pkg.tracer.InstanceSet([bunny] * 64, M)
-    d_moved, d_slicers = queries_of(positions, M, extent, rng)
-    out["b_bunny_8x8"] = {"moved": cells(grid, None, d_moved, "64 copies, moved copies"),
-                          "slicers": cells(grid, None, d_slicers, "64 copies, slicers")}
-    grid.close()
-    del d_moved, d_slicers
+        widest = float(np.ptp(verts, axis=0).max())
+        M = grid_transforms((8, 8), 1.5 * widest, np.random.default_rng(2026))
+        grid = pkg.tracer.InstanceSet([bunny] * 64, M)
+        d_moved, d_slicers = queries_of(positions, M, extent, rng)
+        out["b_bunny_8x8"] = {"moved": cells(grid, None, d_moved, "64 copies, moved copies"),
+                              "slicers": cells(grid, None, d_slicers, "64 copies, slicers")}
+        grid.close()
+        del d_moved, d_slicers
 
-    M = grid_transforms((8, 8), 0.45 * widest, np.random.default_rng(2026))
-    close = pkg.tracer.InstanceSet([bunny] * 64, M)
-    d_cnt = torch.empty((64, triangles), dtype=torch.int32, device="cuda")
+        M = grid_transforms((8, 8), 0.45 * widest, np.random.default_rng(2026))
+        close = pkg.tracer.InstanceSet([bunny] * 64, M)
+        d_cnt = torch.empty((64, triangles), dtype=torch.int32, device="cuda")
 
-    def sweep():
-        for i in range(64):
-            close.instance_intersections_into(i, 0, triangles, 0, 0, d_cnt[i].data_ptr(), 0, True, False, True, stream.cuda_stream)
+        def sweep():
+            for i in range(64):
+                close.instance_intersections_into(i, 0, triangles, 0, 0, d_cnt[i].data_ptr(), 0, True, False, True, stream.cuda_stream)
 
-    r = median_ms(sweep, 64 * triangles)
-    met = d_cnt.cpu().numpy() != 0
-    r.update({"launches": 64, "queries": 64 * triangles, "spacing_over_widest_extent": 0.45, "instances_colliding": int(met.any(1).sum()),
-              "triangles_colliding": round(float(met.mean()), 4)})
-    part = close.instance_intersections(27, max_triangles=0, first=0, count=SAMPLE)[2]
-    r["instance_27_first_4096"] = {"n_mean": round(float(part.mean()), 2), "n_max": int(part.max()), "met": round(float((part > 0).mean()), 4)}
-    out["c_collision_sweep"] = r
-    print(f"  collision sweep: {r}", file=sys.stderr, flush=True)
-    close.close()
-    bunny.close()
-    world.close()
-    text = json.dumps(out)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    print(text)
+        r = time_cell(sweep, 64 * triangles)
+        met = d_cnt.cpu().numpy() != 0
+        r.update({"launches": 64, "queries": 64 * triangles, "spacing_over_widest_extent": 0.45, "instances_colliding": int(met.any(1).sum()),
+                  "triangles_colliding": round(float(met.mean()), 4)})
+        part = close.instance_intersections(27, max_triangles=0, first=0, count=SAMPLE)[2]
+        r["instance_27_first_4096"] = {"n_mean": round(float(part.mean()), 2), "n_max": int(part.max()), "met": round(float((part > 0).mean()), 4)}
+        out["c_collision_sweep"] = r
+        print(f"  collision sweep: {r}", file=sys.stderr, flush=True)
+        close.close()
+    H.emit(out, args)
 
 
 if __name__ == "__main__":

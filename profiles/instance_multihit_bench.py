@@ -10,52 +10,34 @@ the host's merge by the key (wall time, on --compose-rays rays, scaled to a ray)
 
 Every device time is the median of --trials launches after --warmup launches, bracketed by HIP events on the current torch stream.
 Usage: python profiles/instance_multihit_bench.py [--trials 15] [--warmup 5] [--compose-rays 4096]"""
-import argparse
-import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
+import bench_harness as H
+from bench_workloads import down_rays, grid_transforms, through_rays
 
 F = np.float32
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--trials", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = H.parser()
     ap.add_argument("--compose-rays", type=int, default=4096, help="rays of the host composition (it walks instances x rays rays)")
     args = ap.parse_args()
     import torch
     import instance_multi_hit_ref as IM
     import instance_ref as I
-    from instance_bench import down_rays, grid_transforms
-    from multihit_bench import through_rays
-    from __graft_entry__ import load_package
 
-    pkg = load_package()
+    pkg = H.load_package()
     rng = np.random.default_rng(2026)
     stream = torch.cuda.current_stream()
     n = 1 << 20
 
-    def median_ms(fn):
-        for _ in range(args.warmup):
-            fn()
-        times = []
-        for _ in range(args.trials):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            fn()
-            b.record(stream)
-            b.synchronize()
-            times.append(a.elapsed_time(b))
-        return round(float(np.median(times)), 4)
+    median_ms = H.median_timer(args)
 
-    def entry(ms):
+    def entry(t):
+        ms = round(t.ms, 4)
         return {"ms": ms, "Mrays_s": round(n / ms / 1e3, 1)}
 
     def forms(target, d_rays, instanced):
@@ -123,7 +105,7 @@ def main():
                 "leaf_visits": round(c["leaf_visits"] / m, 2), "triangle_tests": round(c["triangle_tests"] / m, 2)}
 
     def device_rays(o, d, tmax):
-        return torch.from_numpy(pkg.tracer.make_rays(o, d, tmax).view(F).reshape(-1, 8).copy()).cuda()
+        return H.upload(pkg.tracer.make_rays(o, d, tmax), 8)
 
     out = {"trials": args.trials, "warmup": args.warmup, "rays": n, "device": torch.cuda.get_device_name(0)}
 
@@ -149,7 +131,7 @@ def main():
     grid.close()
 
     # (c) -----------------------------------------------------------------------------------------------------------------
-    lobed_world = pkg.World(os.path.join(ROOT, "tests", "golden", "lobed_528.trisrc"))
+    lobed_world = pkg.World(os.path.join(H.ROOT, "tests", "golden", "lobed_528.trisrc"))
     lobed = pkg.Scene(lobed_world.flatten())
     lp = np.asarray(lobed_world.arrays()["vertex_positions"], F).reshape(-1, 3)
     size = float(np.ptp(lp, axis=0).max())
@@ -160,7 +142,7 @@ def main():
     out["c_lobed_4096"] = {"instances": len(M), **forms(many, d_rays, True), **retraced(many, d_rays),
                            "host_composition": host_composition(many, lobed, o, d, F(1e7), 4), "per_ray": per_ray(many, o, d, F(1e7))}
     many.close()
-    print(json.dumps(out))
+    H.emit(out, args)
 
 
 if __name__ == "__main__":

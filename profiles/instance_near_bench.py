@@ -12,15 +12,12 @@ with the fastest and the slowest launch.  The walk counters per point (image-box
 instance walks begun) come from one blocking counting run over 2^12 of the same points, and with them the mean near count.
 
 Usage: python profiles/instance_near_bench.py [--trials 15] [--warmup 5] [--points 262144] [--out FILE]"""
-import argparse
-import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
+import bench_harness as H
+from bench_workloads import grid_transforms, near_surface_points
 
 F = np.float32
 SAMPLE = 1 << 12
@@ -29,38 +26,18 @@ RADII = (0.02, 0.10)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--trials", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = H.parser()
     ap.add_argument("--points", type=int, default=1 << 18)
-    ap.add_argument("--out", default=None, help="also write the JSON here")
     args = ap.parse_args()
     import torch
-    from __graft_entry__ import load_package
-    from instance_bench import grid_transforms
-    from instance_point_bench import near_surface_points
 
-    pkg = load_package()
+    pkg = H.load_package()
     stream = torch.cuda.current_stream()
     n = args.points
+    median_ms = H.median_timer(args, slow_ms=1000.0)
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        fn()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b)
-
-    def median_ms(fn):
-        trials, warmup = args.trials, args.warmup
-        if timed(fn) > 1000.0:
-            trials, warmup = 3, 0
-        for _ in range(warmup):
-            fn()
-        times = [timed(fn) for _ in range(trials)]
-        return {"ms": round(float(np.median(times)), 4), "ms_min_max": [round(min(times), 4), round(max(times), 4)], "trials": trials,
-                "Mpoints_s": round(n / float(np.median(times)) / 1e3, 4)}
+    def time_cell(fn):
+        return H.entry(median_ms(fn), "Mpoints_s", n)
 
     def rows(s, plain, pts, extent, what):
         """per radius and K, with and without counts: the set's time and, with `plain` (a Scene), Scene.triangles_within's"""
@@ -79,11 +56,11 @@ def main():
                 d_inst = torch.empty((n, k), dtype=torch.int32, device="cuda")
                 d_cnt = torch.empty(n, dtype=torch.int32, device="cuda")
                 for counts in (True, False):
-                    r = median_ms(lambda: s.triangles_within_into(d_pts.data_ptr(), n, d_out.data_ptr(), d_inst.data_ptr(),
+                    r = time_cell(lambda: s.triangles_within_into(d_pts.data_ptr(), n, d_out.data_ptr(), d_inst.data_ptr(),
                                                                   d_cnt.data_ptr() if counts else 0, k, stream.cuda_stream))
                     if plain is not None:
                         d_plain = torch.empty((n, k, 8), dtype=torch.int32, device="cuda")
-                        p = median_ms(lambda: plain.triangles_within_into(d_pts.data_ptr(), n, d_plain.data_ptr(),
+                        p = time_cell(lambda: plain.triangles_within_into(d_pts.data_ptr(), n, d_plain.data_ptr(),
                                                                           d_cnt.data_ptr() if counts else 0, k, stream.cuda_stream))
                         r = {"instance": r, "scene": p, "instance_over_scene": round(r["ms"] / p["ms"], 3),
                              "same_bytes": bool(torch.equal(d_out, d_plain))}
@@ -96,28 +73,20 @@ def main():
 
     out = {"trials": args.trials, "warmup": args.warmup, "points": n, "device": torch.cuda.get_device_name(0)}
     rng = np.random.default_rng(2026)
-    world = pkg.World(pkg.scenes.bunny_trisrc())
-    positions = np.asarray(world.arrays()["vertex_positions"], F)
-    extent = float(np.ptp(positions.reshape(-1, 3).astype(np.float64), axis=0).max())
-    bunny = pkg.Scene(world.flatten())
-    out["triangles"] = len(positions) // 9
+    with H.bunny_scene(pkg) as (world, bunny, positions):
+        extent = float(np.ptp(positions.reshape(-1, 3).astype(np.float64), axis=0).max())
+        out["triangles"] = len(positions) // 9
 
-    eye = np.eye(3, 4, dtype=F)[None]
-    one = pkg.tracer.InstanceSet([bunny], eye)
-    out["a_identity"] = rows(one, bunny, near_surface_points(positions, eye, n, rng), extent, "one identity instance")
-    one.close()
+        eye = np.eye(3, 4, dtype=F)[None]
+        one = pkg.tracer.InstanceSet([bunny], eye)
+        out["a_identity"] = rows(one, bunny, near_surface_points(positions, eye, n, rng), extent, "one identity instance")
+        one.close()
 
-    M = grid_transforms((8, 8), 1.5 * extent, np.random.default_rng(2026))
-    grid = pkg.tracer.InstanceSet([bunny] * 64, M)
-    out["b_bunny_8x8"] = rows(grid, None, near_surface_points(positions, M, n, rng), extent, "64 copies")
-    grid.close()
-    bunny.close()
-    world.close()
-    text = json.dumps(out)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    print(text)
+        M = grid_transforms((8, 8), 1.5 * extent, np.random.default_rng(2026))
+        grid = pkg.tracer.InstanceSet([bunny] * 64, M)
+        out["b_bunny_8x8"] = rows(grid, None, near_surface_points(positions, M, n, rng), extent, "64 copies")
+        grid.close()
+    H.emit(out, args)
 
 
 if __name__ == "__main__":

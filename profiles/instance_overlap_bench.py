@@ -13,15 +13,12 @@ with the fastest and the slowest launch.  The walk counters per box (image-box t
 walks begun) come from one blocking counting run over 2^12 of the same boxes, and with them the mean count.
 
 Usage: python profiles/instance_overlap_bench.py [--trials 15] [--warmup 5] [--boxes 262144] [--out FILE]"""
-import argparse
-import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
+import bench_harness as H
+from bench_workloads import grid_transforms
 
 F = np.float32
 SAMPLE = 1 << 12
@@ -30,38 +27,19 @@ FORMS = (("counts_only", 0, False), ("K8_counts", 8, False), ("any", 0, True))
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--trials", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = H.parser()
     ap.add_argument("--boxes", type=int, default=1 << 18)
-    ap.add_argument("--out", default=None, help="also write the JSON here")
     args = ap.parse_args()
     import torch
-    from __graft_entry__ import load_package
-    from instance_bench import grid_transforms
     import instance_point_ref as IP
 
-    pkg = load_package()
+    pkg = H.load_package()
     stream = torch.cuda.current_stream()
     n = args.boxes
+    median_ms = H.median_timer(args, slow_ms=1000.0)
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        fn()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b)
-
-    def median_ms(fn):
-        trials, warmup = args.trials, args.warmup
-        if timed(fn) > 1000.0:
-            trials, warmup = 3, 0
-        for _ in range(warmup):
-            fn()
-        times = [timed(fn) for _ in range(trials)]
-        return {"ms": round(float(np.median(times)), 4), "ms_min_max": [round(min(times), 4), round(max(times), 4)], "trials": trials,
-                "Mboxes_s": round(n / float(np.median(times)) / 1e3, 4)}
+    def time_cell(fn):
+        return H.entry(median_ms(fn), "Mboxes_s", n)
 
     def cells(s, plain, d_boxes, what):
         """per form: the set's time and, with `plain` (a Scene), Scene.triangles_in_boxes' on the same boxes"""
@@ -76,12 +54,12 @@ def main():
         d_inst = torch.empty((n, 8), dtype=torch.int32, device="cuda")
         d_cnt = torch.empty(n, dtype=torch.int32, device="cuda")
         for name, k, any_only in FORMS:
-            r = median_ms(lambda: s.triangles_in_boxes_into(d_boxes.data_ptr(), n, d_out.data_ptr() if k else 0, d_inst.data_ptr() if k else 0,
+            r = time_cell(lambda: s.triangles_in_boxes_into(d_boxes.data_ptr(), n, d_out.data_ptr() if k else 0, d_inst.data_ptr() if k else 0,
                                                             d_cnt.data_ptr(), k, any_only, stream.cuda_stream))
             if plain is not None:
                 d_plain = torch.empty((n, 8), dtype=torch.int32, device="cuda")
                 d_plain_cnt = torch.empty(n, dtype=torch.int32, device="cuda")
-                p = median_ms(lambda: plain.triangles_in_boxes_into(d_boxes.data_ptr(), n, d_plain.data_ptr() if k else 0, d_plain_cnt.data_ptr(),
+                p = time_cell(lambda: plain.triangles_in_boxes_into(d_boxes.data_ptr(), n, d_plain.data_ptr() if k else 0, d_plain_cnt.data_ptr(),
                                                                     k, any_only, stream.cuda_stream))
                 r = {"instance": r, "scene": p, "instance_over_scene": round(r["ms"] / p["ms"], 3),
                      "same_answer": bool(torch.equal(d_cnt, d_plain_cnt)) and (k == 0 or bool(torch.equal(d_out, d_plain)))}
@@ -111,38 +89,30 @@ def main():
         A = np.asarray(maps, np.float64)[i]
         centre = np.einsum("nrc,nc->nr", A[:, :, :3], on) + A[:, :, 3]
         half = 0.025 * extent
-        d_near = torch.from_numpy(pkg.tracer.make_boxes(centre - half, centre + half).view(F).reshape(-1, 8).copy()).cuda()
+        d_near = H.upload(pkg.tracer.make_boxes(centre - half, centre + half), 8)
         return d_grid, d_near
 
     out = {"trials": args.trials, "warmup": args.warmup, "boxes": n, "device": torch.cuda.get_device_name(0)}
     rng = np.random.default_rng(2026)
-    world = pkg.World(pkg.scenes.bunny_trisrc())
-    positions = np.asarray(world.arrays()["vertex_positions"], F)
-    verts = positions.reshape(-1, 3).astype(np.float64)
-    extent = float(np.linalg.norm(verts.max(0) - verts.min(0)))
-    bunny = pkg.Scene(world.flatten())
-    out["triangles"] = len(positions) // 9
+    with H.bunny_scene(pkg) as (world, bunny, positions):
+        verts = positions.reshape(-1, 3).astype(np.float64)
+        extent = float(np.linalg.norm(verts.max(0) - verts.min(0)))
+        out["triangles"] = len(positions) // 9
 
-    eye = np.eye(3, 4, dtype=F)[None]
-    one = pkg.tracer.InstanceSet([bunny], eye)
-    d_grid, d_near = boxes_of(positions, eye, extent, rng)
-    out["a_identity"] = {f"grid{GRID}": cells(one, bunny, d_grid, "one identity instance, grid cells"),
-                         "surface_5pct": cells(one, bunny, d_near, "one identity instance, 5 % boxes")}
-    one.close()
+        eye = np.eye(3, 4, dtype=F)[None]
+        one = pkg.tracer.InstanceSet([bunny], eye)
+        d_grid, d_near = boxes_of(positions, eye, extent, rng)
+        out["a_identity"] = {f"grid{GRID}": cells(one, bunny, d_grid, "one identity instance, grid cells"),
+                             "surface_5pct": cells(one, bunny, d_near, "one identity instance, 5 % boxes")}
+        one.close()
 
-    M = grid_transforms((8, 8), 1.5 * float(np.ptp(verts, axis=0).max()), np.random.default_rng(2026))
-    grid = pkg.tracer.InstanceSet([bunny] * 64, M)
-    d_grid, d_near = boxes_of(positions, M, extent, rng)
-    out["b_bunny_8x8"] = {f"grid{GRID}": cells(grid, None, d_grid, "64 copies, grid cells"),
-                          "surface_5pct": cells(grid, None, d_near, "64 copies, 5 % boxes")}
-    grid.close()
-    bunny.close()
-    world.close()
-    text = json.dumps(out)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    print(text)
+        M = grid_transforms((8, 8), 1.5 * float(np.ptp(verts, axis=0).max()), np.random.default_rng(2026))
+        grid = pkg.tracer.InstanceSet([bunny] * 64, M)
+        d_grid, d_near = boxes_of(positions, M, extent, rng)
+        out["b_bunny_8x8"] = {f"grid{GRID}": cells(grid, None, d_grid, "64 copies, grid cells"),
+                              "surface_5pct": cells(grid, None, d_near, "64 copies, 5 % boxes")}
+        grid.close()
+    H.emit(out, args)
 
 
 if __name__ == "__main__":

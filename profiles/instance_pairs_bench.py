@@ -21,49 +21,28 @@ Every time is the median of --trials launches after --warmup launches, bracketed
 with the fastest and the slowest launch.
 
 Usage: python profiles/instance_pairs_bench.py [--trials 15] [--warmup 5] [--out FILE]"""
-import argparse
-import json
 import os
 import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
+import bench_harness as H
+from bench_workloads import grid_transforms
 
 F = np.float32
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--trials", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "instance_pairs_bench.json"))
-    args = ap.parse_args()
+    args = H.parser(out=os.path.join(H.ROOT, "profiles", "instance_pairs_bench.json")).parse_args()
     import torch
-    from __graft_entry__ import load_package
-    from instance_bench import grid_transforms
 
-    pkg = load_package()
+    pkg = H.load_package()
     stream = torch.cuda.current_stream()
+    median_ms = H.median_timer(args, slow_ms=500.0)
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        fn()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b)
-
-    def median_ms(fn):
-        trials, warmup = args.trials, args.warmup
-        if timed(fn) > 500.0:
-            trials, warmup = 3, 0
-        for _ in range(warmup):
-            fn()
-        times = [timed(fn) for _ in range(trials)]
-        return {"ms": round(float(np.median(times)), 4), "ms_min_max": [round(min(times), 4), round(max(times), 4)], "trials": trials}
+    def time_cell(fn):
+        return H.entry(median_ms(fn))
 
     def rows(s, what):
         n = s.count
@@ -75,11 +54,11 @@ def main():
         segment = torch.repeat_interleave(torch.arange(n, device="cuda"), torch.as_tensor(triangles, device="cuda"))
         res = {"instances": n, "query_triangles": int(starts[-1])}
         sp = stream.cuda_stream
-        res["any"] = median_ms(lambda: s.collision_pairs_into(0, counts.data_ptr(), any_only=True, stream_ptr=sp))
+        res["any"] = time_cell(lambda: s.collision_pairs_into(0, counts.data_ptr(), any_only=True, stream_ptr=sp))
         matrix = counts.cpu().numpy().reshape(n, n) != 0
-        res["any_upper"] = median_ms(lambda: s.collision_pairs_into(0, counts.data_ptr(), any_only=True, upper=True, stream_ptr=sp))
-        res["first_only"] = median_ms(lambda: s.collision_pairs_into(first.data_ptr(), 0, stream_ptr=sp))
-        res["counts"] = median_ms(lambda: s.collision_pairs_into(first.data_ptr(), counts.data_ptr(), stream_ptr=sp))
+        res["any_upper"] = time_cell(lambda: s.collision_pairs_into(0, counts.data_ptr(), any_only=True, upper=True, stream_ptr=sp))
+        res["first_only"] = time_cell(lambda: s.collision_pairs_into(first.data_ptr(), 0, stream_ptr=sp))
+        res["counts"] = time_cell(lambda: s.collision_pairs_into(first.data_ptr(), counts.data_ptr(), stream_ptr=sp))
         full = counts.cpu().numpy().reshape(n, n)
         assert np.array_equal(full > 0, matrix)
         colliding = torch.zeros(n, dtype=torch.int32, device="cuda")
@@ -91,7 +70,7 @@ def main():
             colliding.index_add_(0, segment, flags)
             return colliding.cpu()
 
-        res["loop_any"] = median_ms(loop)
+        res["loop_any"] = time_cell(loop)
         res["rows_equal"] = bool(np.array_equal(loop().numpy() > 0, matrix.any(1)))
         a, b = res["any"], res["loop_any"]
         res["any_over_loop"] = {"ratio": round(a["ms"] / b["ms"], 4),
@@ -110,21 +89,17 @@ def main():
         return res
 
     out = {"trials": args.trials, "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
-    world = pkg.World(pkg.scenes.bunny_trisrc())
-    pos = np.asarray(world.arrays()["vertex_positions"], F)
-    bunny = pkg.Scene(world.flatten())
-    extent = float(np.ptp(pos.reshape(-1, 3).astype(np.float64), axis=0).max())
-    out["triangles"] = len(pos) // 9
-    M = grid_transforms((8, 8), 1.5 * extent, np.random.default_rng(2026))
-    grid = pkg.tracer.InstanceSet([bunny] * 64, M)
-    out["a_bunny_8x8"] = rows(grid, "64 copies, 1.5 extents apart")
-    close = M.copy()
-    close[:, :, 3] *= F(0.45 / 1.5)
-    grid.update(close)
-    out["b_bunny_8x8_close"] = rows(grid, "64 copies, 0.45 extents apart")
-    grid.close()
-    bunny.close()
-    world.close()
+    with H.bunny_scene(pkg) as (world, bunny, pos):
+        extent = float(np.ptp(pos.reshape(-1, 3).astype(np.float64), axis=0).max())
+        out["triangles"] = len(pos) // 9
+        M = grid_transforms((8, 8), 1.5 * extent, np.random.default_rng(2026))
+        grid = pkg.tracer.InstanceSet([bunny] * 64, M)
+        out["a_bunny_8x8"] = rows(grid, "64 copies, 1.5 extents apart")
+        close = M.copy()
+        close[:, :, 3] *= F(0.45 / 1.5)
+        grid.update(close)
+        out["b_bunny_8x8_close"] = rows(grid, "64 copies, 0.45 extents apart")
+        grid.close()
 
     import test_gpu_instance_point as G
     names, maps, _ = G.the_set(pkg, "301 tiny instances")
@@ -133,11 +108,7 @@ def main():
     tiny.close()
     for _, sc in G._members.values():
         sc.close()
-    text = json.dumps(out)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
-    print(text)
+    H.emit(out, args)
 
 
 if __name__ == "__main__":

@@ -16,66 +16,30 @@ visits, triangle tests, and instance walks begun) come from one blocking countin
 are Scene.closest_points' own, so the other rows' against them say what the looser image boxes and the top level cost.
 
 Usage: python profiles/instance_point_bench.py [--trials 15] [--warmup 5] [--points 1048576]"""
-import argparse
-import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
+import bench_harness as H
+from bench_workloads import grid_transforms, near_surface_points
 
 F = np.float32
 SAMPLE = 1 << 12
 
 
-def near_surface_points(positions, maps, n, rng):
-    """world points [n, 4] float32 (max_dist2 = +inf) near the surfaces of the placed copies of `positions`"""
-    tris = positions.reshape(-1, 3, 3).astype(np.float64)
-    extent = float(np.ptp(tris.reshape(-1, 3), axis=0).max())
-    i, t = rng.integers(0, len(maps), n), rng.integers(0, len(tris), n)
-    on = tris[t].mean(1) + rng.normal(size=(n, 3)) * extent / 100
-    A = maps.astype(np.float64)
-    out = np.full((n, 4), np.inf, F)
-    out[:, :3] = np.einsum("nrc,nc->nr", A[i, :, :3], on) + A[i, :, 3]
-    return out
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--trials", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = H.parser()
     ap.add_argument("--points", type=int, default=1 << 20)
     args = ap.parse_args()
     import torch
-    from __graft_entry__ import load_package
-    from instance_bench import grid_transforms
 
-    pkg = load_package()
+    pkg = H.load_package()
     stream = torch.cuda.current_stream()
     n = args.points
+    median_ms = H.median_timer(args, slow_ms=2000.0)
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        fn()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b)
-
-    def median_ms(fn):
-        trials, warmup = args.trials, args.warmup
-        if timed(fn) > 2000.0:
-            trials, warmup = 3, 0
-        for _ in range(warmup):
-            fn()
-        times = [timed(fn) for _ in range(trials)]
-        return float(np.median(times)), float(min(times)), float(max(times)), trials
-
-    def entry(points, ms, lo, hi, trials):
-        return {"points": points, "ms": round(ms, 4), "ms_min_max": [round(lo, 4), round(hi, 4)], "trials": trials,
-                "Mpoints_s": round(points / ms / 1e3, 4)}
+    def entry(points, t):
+        return H.entry(t, "Mpoints_s", points, points=points)
 
     def per_point(c, count):
         return {key: round(c[key] / count, 2) for key in ("node_visits", "leaf_visits", "triangle_tests", "traversals")}
@@ -84,8 +48,8 @@ def main():
         d_pts = torch.from_numpy(pts).cuda()
         d_out = torch.empty((len(pts), 8), dtype=torch.int32, device="cuda")
         d_inst = torch.empty(len(pts), dtype=torch.int32, device="cuda")
-        r = entry(len(pts), *median_ms(lambda: s.closest_points_into(d_pts.data_ptr(), len(pts), d_out.data_ptr(), d_inst.data_ptr(),
-                                                                     stream.cuda_stream)))
+        r = entry(len(pts), median_ms(lambda: s.closest_points_into(d_pts.data_ptr(), len(pts), d_out.data_ptr(), d_inst.data_ptr(),
+                                                                    stream.cuda_stream)))
         r["instances"] = s.count
         r["hit_fraction"] = round(float((d_inst >= 0).float().mean()), 4)
         _, _, c = s.closest_points(pts[:SAMPLE], counters=True)
@@ -97,71 +61,63 @@ def main():
     rng = np.random.default_rng(2026)
 
     # (a) -----------------------------------------------------------------------------------------------------------------
-    world = pkg.World(pkg.scenes.bunny_trisrc())
-    positions = np.asarray(world.arrays()["vertex_positions"], F)
-    bunny = pkg.Scene(world.flatten())
-    eye = np.eye(3, 4, dtype=F)[None]
-    one = pkg.tracer.InstanceSet([bunny], eye)
-    pts = near_surface_points(positions, eye, n, rng)
-    row, d_pts, d_out, _ = set_row(one, pts)
-    d_plain = torch.empty((n, 8), dtype=torch.int32, device="cuda")
-    plain = entry(n, *median_ms(lambda: bunny.closest_points_into(d_pts.data_ptr(), n, d_plain.data_ptr(), stream.cuda_stream)))
-    _, c = bunny.closest_points(pts[:SAMPLE], counters=True)
-    plain["per_point"] = per_point(c, min(SAMPLE, n))
-    out["a_identity"] = {"triangles": len(positions) // 9, "instance": row, "scene": plain, "instance_over_scene": round(row["ms"] / plain["ms"], 3),
-                         "same_bytes": bool(torch.equal(d_out, d_plain))}
-    one.close()
+    with H.bunny_scene(pkg) as (world, bunny, positions):
+        eye = np.eye(3, 4, dtype=F)[None]
+        one = pkg.tracer.InstanceSet([bunny], eye)
+        pts = near_surface_points(positions, eye, n, rng)
+        row, d_pts, d_out, _ = set_row(one, pts)
+        d_plain = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+        plain = entry(n, median_ms(lambda: bunny.closest_points_into(d_pts.data_ptr(), n, d_plain.data_ptr(), stream.cuda_stream)))
+        _, c = bunny.closest_points(pts[:SAMPLE], counters=True)
+        plain["per_point"] = per_point(c, min(SAMPLE, n))
+        out["a_identity"] = {"triangles": len(positions) // 9, "instance": row, "scene": plain, "instance_over_scene": round(row["ms"] / plain["ms"], 3),
+                             "same_bytes": bool(torch.equal(d_out, d_plain))}
+        one.close()
 
-    # (b) -----------------------------------------------------------------------------------------------------------------
-    extent = float(np.ptp(positions.reshape(-1, 3).astype(np.float64), axis=0).max())
-    M = grid_transforms((8, 8), 1.5 * extent, np.random.default_rng(2026))
-    grid = pkg.tracer.InstanceSet([bunny] * 64, M)
-    out["b_bunny_8x8"] = set_row(grid, near_surface_points(positions, M, n, rng))[0]
-    grid.close()
+        # (b) -----------------------------------------------------------------------------------------------------------------
+        extent = float(np.ptp(positions.reshape(-1, 3).astype(np.float64), axis=0).max())
+        M = grid_transforms((8, 8), 1.5 * extent, np.random.default_rng(2026))
+        grid = pkg.tracer.InstanceSet([bunny] * 64, M)
+        out["b_bunny_8x8"] = set_row(grid, near_surface_points(positions, M, n, rng))[0]
+        grid.close()
 
-    M = grid_transforms((8, 8), 1.5 * extent, np.random.default_rng(2026), scale=(1.0, 1.0))
-    grid = pkg.tracer.InstanceSet([bunny] * 64, M)
-    row, d_pts, d_out, d_inst = set_row(grid, near_surface_points(positions, M, n, rng))
-    d_W = torch.from_numpy(grid.world_to_object()).cuda()
-    moved = torch.empty((n, 4), dtype=torch.float32, device="cuda")
-    rec = torch.empty((n, 8), dtype=torch.int32, device="cuda")
-    best = torch.empty((n, 8), dtype=torch.int32, device="cuda")
-    best_inst = torch.empty(n, dtype=torch.int32, device="cuda")
+        M = grid_transforms((8, 8), 1.5 * extent, np.random.default_rng(2026), scale=(1.0, 1.0))
+        grid = pkg.tracer.InstanceSet([bunny] * 64, M)
+        row, d_pts, d_out, d_inst = set_row(grid, near_surface_points(positions, M, n, rng))
+        d_W = torch.from_numpy(grid.world_to_object()).cuda()
+        moved = torch.empty((n, 4), dtype=torch.float32, device="cuda")
+        rec = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+        best = torch.empty((n, 8), dtype=torch.int32, device="cuda")
+        best_inst = torch.empty(n, dtype=torch.int32, device="cuda")
 
-    def caller_loop():
-        """what a caller writes today for rigid maps: per instance the points into object space, the plain query, the nearer kept"""
-        best[:, 3] = torch.tensor(float("inf")).view(torch.int32).item()
-        best[:, 6] = -1
-        best_inst.fill_(-1)
-        for i in range(64):
-            moved[:, :3] = d_pts[:, :3] @ d_W[i, :, :3].T + d_W[i, :, 3]
-            moved[:, 3] = d_pts[:, 3]
-            bunny.closest_points_into(moved.data_ptr(), n, rec.data_ptr(), stream.cuda_stream)
-            nearer = (rec[:, 6] >= 0) & (rec[:, 3].view(torch.float32) < best[:, 3].view(torch.float32))
-            best[nearer] = rec[nearer]
-            best_inst[nearer] = i
+        def caller_loop():
+            """what a caller writes today for rigid maps: per instance the points into object space, the plain query, the nearer kept"""
+            best[:, 3] = torch.tensor(float("inf")).view(torch.int32).item()
+            best[:, 6] = -1
+            best_inst.fill_(-1)
+            for i in range(64):
+                moved[:, :3] = d_pts[:, :3] @ d_W[i, :, :3].T + d_W[i, :, 3]
+                moved[:, 3] = d_pts[:, 3]
+                bunny.closest_points_into(moved.data_ptr(), n, rec.data_ptr(), stream.cuda_stream)
+                nearer = (rec[:, 6] >= 0) & (rec[:, 3].view(torch.float32) < best[:, 3].view(torch.float32))
+                best[nearer] = rec[nearer]
+                best_inst[nearer] = i
 
-    loop = entry(n, *median_ms(caller_loop))
-    agree = (best_inst == d_inst) & (best[:, 6] == d_out[:, 6])
-    out["b_rigid_8x8"] = {"set": row, "caller_loop": loop, "loop_over_set": round(loop["ms"] / row["ms"], 2),
-                          "same_instance_and_triangle": round(float(agree.float().mean()), 6)}
-    grid.close()
-    bunny.close()
-    world.close()
+        loop = entry(n, median_ms(caller_loop))
+        agree = (best_inst == d_inst) & (best[:, 6] == d_out[:, 6])
+        out["b_rigid_8x8"] = {"set": row, "caller_loop": loop, "loop_over_set": round(loop["ms"] / row["ms"], 2),
+                              "same_instance_and_triangle": round(float(agree.float().mean()), 6)}
+        grid.close()
     del d_pts, d_out, d_inst, moved, rec, best, best_inst, d_plain
 
     # (c) -----------------------------------------------------------------------------------------------------------------
-    world = pkg.World(os.path.join(ROOT, "tests", "golden", "lobed_528.trisrc"))
-    positions = np.asarray(world.arrays()["vertex_positions"], F)
-    lobed = pkg.Scene(world.flatten())
-    extent = float(np.ptp(positions.reshape(-1, 3).astype(np.float64), axis=0).max())
-    M = grid_transforms((16, 16, 16), 1.5 * extent, np.random.default_rng(2027))
-    grid = pkg.tracer.InstanceSet([lobed] * 4096, M)
-    out["c_lobed_4096"] = set_row(grid, near_surface_points(positions, M, n, rng))[0]
-    grid.close()
-    lobed.close()
-    world.close()
-    print(json.dumps(out))
+    with H.lobed_scene(pkg) as (world, lobed, positions):
+        extent = float(np.ptp(positions.reshape(-1, 3).astype(np.float64), axis=0).max())
+        M = grid_transforms((16, 16, 16), 1.5 * extent, np.random.default_rng(2027))
+        grid = pkg.tracer.InstanceSet([lobed] * 4096, M)
+        out["c_lobed_4096"] = set_row(grid, near_surface_points(positions, M, n, rng))[0]
+        grid.close()
+    H.emit(out, args)
 
 
 if __name__ == "__main__":

@@ -9,17 +9,14 @@
 
 Usage: python profiles/instance_update_bench.py [--trials 10] [--warmup 3] [--sizes 64,4096,65536,1048576]
        python profiles/instance_update_bench.py --trace-only   (device updates at 65,536 instances only, for a trace)"""
-import argparse
 import ctypes as C
 import json
 import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
+import bench_harness as H
 
 F = np.float32
 GRIDS = {64: (4, 4, 4), 4096: (16, 16, 16), 65536: (64, 32, 32), 1 << 20: (128, 128, 64)}
@@ -50,35 +47,24 @@ def set_arrays(s):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--trials", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap = H.parser(trials=10, warmup=3)
     ap.add_argument("--sizes", default="64,4096,65536,1048576")
     ap.add_argument("--trace-only", action="store_true")
     args = ap.parse_args()
     import torch
-    from __graft_entry__ import load_package
 
-    pkg = load_package()
+    pkg = H.load_package()
     rng = np.random.default_rng(2026)
     stream = torch.cuda.current_stream()
-    world = pkg.World(os.path.join(ROOT, "tests", "golden", "lobed_528.trisrc"))
+    world = pkg.World(os.path.join(H.ROOT, "tests", "golden", "lobed_528.trisrc"))
     lobed = pkg.Scene(world.flatten())
     lp = np.asarray(world.arrays()["vertex_positions"], F).reshape(-1, 3)
     size = float(np.ptp(lp, axis=0).max())
 
-    def events_ms(fn, trials, warmup):
-        for _ in range(warmup):
-            fn()
-        times = []
-        for _ in range(trials):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            fn()
-            b.record(stream)
-            b.synchronize()
-            times.append(a.elapsed_time(b))
-        return round(float(np.median(times)), 4)
+    timing = H.median_timer(args)
+
+    def events_ms(fn):
+        return round(timing(fn).ms, 4)
 
     def moved(M):
         M2 = M.copy()
@@ -118,7 +104,7 @@ def main():
         def device_update():
             s.update_into(d_M[flip[0] % 2].data_ptr(), stream.cuda_stream)
             flip[0] += 1
-        ms = events_ms(device_update, args.trials, args.warmup)
+        ms = events_ms(device_update)
         # the enqueue alone (the host cost of a device update), and the equality of the two built sets
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -152,7 +138,7 @@ def main():
     dvec = aim - o
     dvec = (dvec / np.linalg.norm(dvec, axis=1, keepdims=True)).astype(F)
     rays = pkg.tracer.make_rays(o, dvec, F(1e7))
-    d_rays = torch.from_numpy(rays.view(np.float32).reshape(-1, 8).copy()).cuda()
+    d_rays = H.upload(rays, 8)
     hits = torch.empty((nr, 4), dtype=torch.int32, device="cuda")
     inst = torch.empty(nr, dtype=torch.int32, device="cuda")
     d_M = torch.from_numpy(M).cuda()
@@ -172,13 +158,13 @@ def main():
 
     def trace_only():
         s.trace_rays_into(d_rays.data_ptr(), nr, hits.data_ptr(), inst.data_ptr(), stream.cuda_stream)
-    out["b_step_4096"] = {"rays": nr, "device_update_step_ms": events_ms(device_step, args.trials, args.warmup),
-                          "host_update_step_ms": events_ms(host_step, args.trials, args.warmup),
-                          "trace_alone_ms": events_ms(trace_only, args.trials, args.warmup)}
+    out["b_step_4096"] = {"rays": nr, "device_update_step_ms": events_ms(device_step),
+                          "host_update_step_ms": events_ms(host_step),
+                          "trace_alone_ms": events_ms(trace_only)}
     s.close()
     ref.close()
     own.close()
-    print(json.dumps(out))
+    H.emit(out, args)
 
 
 if __name__ == "__main__":

@@ -16,16 +16,12 @@ evaluated, leaf visits, triangle tests) come from one blocking counting run over
                 ratio of the times and whether indices and counts agree
 
 Usage: python profiles/intersect_bench.py [--trials 15] [--warmup 5] [--no-million]"""
-import argparse
 import ctypes as C
-import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
+import bench_harness as H
 
 F = np.float32
 COUNT = 1 << 20
@@ -80,41 +76,21 @@ def torch_intersect(pos, queries, k, chunk=256):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--trials", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = H.parser()
     ap.add_argument("--no-million", action="store_true")
     args = ap.parse_args()
     import torch
-    from __graft_entry__ import load_package
     import intersect_cases as IC
     import intersect_ref as IR
 
-    pkg = load_package()
+    pkg = H.load_package()
     N = pkg._native
     lib = N.load_intersect()
     stream = torch.cuda.current_stream()
+    median_ms = H.median_timer(args, slow_ms=500.0)
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        fn()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b)
-
-    def median_ms(fn):
-        trials, warmup = args.trials, args.warmup
-        if timed(fn) > 500.0:
-            trials, warmup = 3, 0
-        for _ in range(warmup):
-            fn()
-        times = [timed(fn) for _ in range(trials)]
-        return float(np.median(times)), float(min(times)), float(max(times)), trials
-
-    def entry(queries, ms, lo, hi, trials):
-        return {"queries": queries, "ms": round(ms, 4), "ms_min_max": [round(lo, 4), round(hi, 4)], "trials": trials,
-                "Mqueries_s": round(queries / ms / 1e3, 4)}
+    def entry(queries, t):
+        return H.entry(t, "Mqueries_s", queries, queries=queries)
 
     def launcher(scene, d_queries, count, k, any_only, skip, d_out, d_cnt):
         """the item form on d_queries, or with d_queries None the self form over the first `count` triangles"""
@@ -134,7 +110,7 @@ def main():
         triangles [<= 2^12, 3, 3]: of the same queries)"""
         d_out = torch.empty((count, 8), dtype=torch.int32, device="cuda")
         d_cnt = torch.empty(count, dtype=torch.int32, device="cuda")
-        r = entry(count, *median_ms(launcher(scene, d_queries, count, k, any_only, skip, d_out, d_cnt)))
+        r = entry(count, median_ms(launcher(scene, d_queries, count, k, any_only, skip, d_out, d_cnt)))
         full = d_cnt.cpu().numpy()
         r["n_mean"], r["n_max"], r["nonzero"] = round(float(full.mean()), 3), int(full.max()), round(float((full > 0).mean()), 4)
         _, _, c = scene.intersecting_triangles(sample, max_triangles=k, counters=True, any_only=any_only, skip_shared=skip)
@@ -151,7 +127,7 @@ def main():
                "self_K8_skip": row(scene, tris[pick], None, T, 8, False, True),
                "self_K8": row(scene, tris[pick], None, T, 8, False, False)}
         moved = IC.moved_copy(pos, seed=8)
-        d_moved = torch.from_numpy(IR.make_triangles(moved).view(F).reshape(-1, 12).copy()).cuda()
+        d_moved = H.upload(IR.make_triangles(moved), 12)
         res["moved_K8"] = row(scene, moved[pick], d_moved, T, 8, False, False)
         res["moved_any"] = row(scene, moved[pick], d_moved, T, 0, True, False)
         # slicing triangles of about 5 % of the diagonal (corners on a circle of that diameter) about random surface points
@@ -161,7 +137,7 @@ def main():
         w /= w.sum(1, keepdims=True)
         centre = (tris[t] * w[:, :, None]).sum(1)
         slicers = (unit_slicers(COUNT, 11) * (0.025 * diagonal) + centre[:, None, :]).astype(F)
-        d_slicers = torch.from_numpy(IR.make_triangles(slicers).view(F).reshape(-1, 12).copy()).cuda()
+        d_slicers = H.upload(IR.make_triangles(slicers), 12)
         some = slicers[:SAMPLE]
         res["slicers_counts"] = row(scene, some, d_slicers, COUNT, 0, False, False)
         res["slicers_K8"] = row(scene, some, d_slicers, COUNT, 8, False, False)
@@ -179,25 +155,21 @@ def main():
         return np.cos(angles)[:, :, None] * u[:, None, :] + np.sin(angles)[:, :, None] * w[:, None, :]
 
     out = {"trials": args.trials, "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
-    world = pkg.World(pkg.scenes.bunny_trisrc())
-    pos = np.asarray(world.arrays()["vertex_positions"], F)
-    scene = pkg.Scene(world.flatten())
-    out["bunny"], d_slicers = scene_cases(scene, pos)
-    out["bunny"]["triangles"] = len(pos) // 9
+    with H.bunny_scene(pkg) as (world, scene, pos):
+        out["bunny"], d_slicers = scene_cases(scene, pos)
+        out["bunny"]["triangles"] = len(pos) // 9
 
-    # what a caller would write today: every query against every triangle in torch, on 2^12 of the slicers
-    few = d_slicers[:SAMPLE].contiguous()
-    d_pos = torch.from_numpy(pos).cuda()
-    want, want_n = torch_intersect(d_pos, few, 8)
-    got, got_n = scene.intersecting_triangles(few, max_triangles=8)
-    d_out = torch.empty((len(few), 8), dtype=torch.int32, device="cuda")
-    d_cnt = torch.empty(len(few), dtype=torch.int32, device="cuda")
-    ours = entry(len(few), *median_ms(launcher(scene, few, len(few), 8, False, False, d_out, d_cnt)))
-    brute = entry(len(few), *median_ms(lambda: torch_intersect(d_pos, few, 8)))
-    out["torch_vs_k8"] = {"kernel": ours, "torch": brute, "torch_over_kernel": round(brute["ms"] / ours["ms"], 2),
-                          "indices_agree": bool((got == want).all()), "counts_agree": bool((got_n == want_n).all())}
-    scene.close()
-    world.close()
+        # what a caller would write today: every query against every triangle in torch, on 2^12 of the slicers
+        few = d_slicers[:SAMPLE].contiguous()
+        d_pos = torch.from_numpy(pos).cuda()
+        want, want_n = torch_intersect(d_pos, few, 8)
+        got, got_n = scene.intersecting_triangles(few, max_triangles=8)
+        d_out = torch.empty((len(few), 8), dtype=torch.int32, device="cuda")
+        d_cnt = torch.empty(len(few), dtype=torch.int32, device="cuda")
+        ours = entry(len(few), median_ms(launcher(scene, few, len(few), 8, False, False, d_out, d_cnt)))
+        brute = entry(len(few), median_ms(lambda: torch_intersect(d_pos, few, 8)))
+        out["torch_vs_k8"] = {"kernel": ours, "torch": brute, "torch_over_kernel": round(brute["ms"] / ours["ms"], 2),
+                              "indices_agree": bool((got == want).all()), "counts_agree": bool((got_n == want_n).all())}
 
     if not args.no_million:
         dw = pkg.tracer.DeviceWorld(pkg.scenes.million_obj())
@@ -205,7 +177,7 @@ def main():
         out["million"], _ = scene_cases(dw.scene, pos)
         out["million"]["triangles"] = len(pos) // 9
         dw.close()
-    print(json.dumps(out))
+    H.emit(out, args)
 
 
 if __name__ == "__main__":

@@ -11,79 +11,41 @@ Per scene and ray set:
 Every time is the median of --trials launches after --warmup launches, bracketed by HIP events on the current torch stream.
 The counters per ray are those of the walk that skips nothing (one blocking counting run) and of the closest-hit walk.
 Usage: python profiles/multihit_bench.py [--trials 15] [--warmup 5] [--no-million]"""
-import argparse
-import json
-import os
-import sys
-
-import numpy as np
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
-
-F = np.float32
-
-
-def through_rays(positions, n, seed):
-    """origins on a sphere of 1.5 box diagonals around the box centre, aimed at uniform points of the box; tmax 1e7"""
-    rng = np.random.default_rng(seed)
-    v = positions.reshape(-1, 3).astype(np.float64)
-    lo, hi = v.min(0), v.max(0)
-    centre, radius = (lo + hi) / 2, 1.5 * np.linalg.norm(hi - lo)
-    s = rng.normal(size=(n, 3))
-    o = centre + radius * s / np.linalg.norm(s, axis=1, keepdims=True)
-    d = lo + (hi - lo) * rng.random((n, 3)) - o
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    return o.astype(F), d.astype(F), np.full(n, F(1e7))
+import bench_harness as H
+from bench_workloads import morton_order, through_rays
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--trials", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = H.parser()
     ap.add_argument("--no-million", action="store_true")
     args = ap.parse_args()
     import torch
     import ray_query_ref as R
-    from __graft_entry__ import load_package
-    from point_query_bench import morton_order
     from test_gpu_ray_query import random_rays
 
-    pkg = load_package()
+    pkg = H.load_package()
     stream = torch.cuda.current_stream()
     n = 1 << 20
+    median_ms = H.median_timer(args)
 
-    def median_ms(fn):
-        for _ in range(args.warmup):
-            fn()
-        times = []
-        for _ in range(args.trials):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            fn()
-            b.record(stream)
-            b.synchronize()
-            times.append(a.elapsed_time(b))
-        return float(np.median(times)), float(min(times)), float(max(times))
-
-    def entry(ms, lo, hi):
-        return {"ms": round(ms, 4), "ms_min_max": [round(lo, 4), round(hi, 4)], "Mrays_s": round(n / ms / 1e3, 1)}
+    def entry(t):
+        return H.entry(t, "Mrays_s", n, places=1, trials=False)
 
     def case(scene, o, d, tmax):
         rays = pkg.tracer.make_rays(o, d, tmax)
-        d_rays = torch.from_numpy(rays.view(F).reshape(-1, 8).copy()).cuda()
+        d_rays = H.upload(rays, 8)
         d_hits = torch.empty((n, 8, 4), dtype=torch.int32, device="cuda")
         d_counts = torch.empty(n, dtype=torch.int32, device="cuda")
         out = {}
         for k in (1, 4, 8):
             for with_counts in (True, False):
-                out[f"first_{k}" + ("_with_counts" if with_counts else "")] = entry(*median_ms(lambda: scene.trace_all_hits_into(
+                out[f"first_{k}" + ("_with_counts" if with_counts else "")] = entry(median_ms(lambda: scene.trace_all_hits_into(
                     d_rays.data_ptr(), n, d_hits.data_ptr(), d_counts.data_ptr() if with_counts else 0, k, stream.cuda_stream)))
-        out["counts_only"] = entry(*median_ms(lambda: scene.trace_all_hits_into(d_rays.data_ptr(), n, 0, d_counts.data_ptr(), 0,
-                                                                               stream.cuda_stream)))
+        out["counts_only"] = entry(median_ms(lambda: scene.trace_all_hits_into(d_rays.data_ptr(), n, 0, d_counts.data_ptr(), 0,
+                                                                              stream.cuda_stream)))
         d_one = torch.empty((n, 4), dtype=torch.float32, device="cuda")
-        out["trace_rays_closest"] = entry(*median_ms(lambda: scene.trace_rays_into(d_rays.data_ptr(), n, d_one.data_ptr(),
-                                                                                  stream.cuda_stream, max_bvh_iterations=0)))
+        out["trace_rays_closest"] = entry(median_ms(lambda: scene.trace_rays_into(d_rays.data_ptr(), n, d_one.data_ptr(),
+                                                                                 stream.cuda_stream, max_bvh_iterations=0)))
         work = torch.empty_like(d_rays)
 
         def retrace(k):
@@ -96,7 +58,7 @@ def main():
                 work[:, 3] = torch.where(hit, work[:, 3] - t, torch.zeros_like(t))   # a miss ends the ray (tmax 0: no walk)
 
         for k in (4, 8):
-            out[f"retrace_{k}_calls"] = entry(*median_ms(lambda: retrace(k)))
+            out[f"retrace_{k}_calls"] = entry(median_ms(lambda: retrace(k)))
         _, counts, c = scene.trace_all_hits(rays, max_hits=0, counters=True)
         _, cc = scene.trace_rays(rays, max_bvh_iterations=0, counters=True)
         out["per_ray"] = {"crossings": round(float(counts.mean()), 3), "crossings_max": int(counts.max()),
@@ -109,18 +71,15 @@ def main():
     out = {"trials": args.trials, "warmup": args.warmup, "rays": n, "device": torch.cuda.get_device_name(0)}
     scenes = [("bunny", pkg.scenes.bunny_trisrc)] + ([] if args.no_million else [("million", pkg.scenes.million_obj)])
     for name, path in scenes:
-        world = pkg.World(path())
-        arrays = R.SceneArrays(world.arrays())
-        scene = pkg.Scene(world.flatten())
-        scene.set_kernel(0)
-        o, d, tmax = through_rays(arrays.positions, n, seed=2026)
-        order = morton_order(o)
-        out[name] = {"triangles": len(arrays.positions),
-                     "through": case(scene, o[order], d[order], tmax[order]),
-                     "random": case(scene, *random_rays(arrays, n, seed=2027))}
-        scene.close()
-        world.close()
-    print(json.dumps(out))
+        with H.scene_of(pkg, path()) as (world, scene, _):
+            arrays = R.SceneArrays(world.arrays())
+            scene.set_kernel(0)
+            o, d, tmax = through_rays(arrays.positions, n, seed=2026)
+            order = morton_order(o)
+            out[name] = {"triangles": len(arrays.positions),
+                         "through": case(scene, o[order], d[order], tmax[order]),
+                         "random": case(scene, *random_rays(arrays, n, seed=2027))}
+    H.emit(out, args)
 
 
 if __name__ == "__main__":

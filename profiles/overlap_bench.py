@@ -12,16 +12,12 @@ from one blocking counting run of 2^12 of the boxes, for the counting form and f
                 (every box against every triangle: what a caller would write without this query)
 
 Usage: python profiles/overlap_bench.py [--trials 15] [--warmup 5] [--no-million]"""
-import argparse
 import ctypes as C
-import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
+import bench_harness as H
 
 F = np.float32
 COUNT = 1 << 20
@@ -63,39 +59,19 @@ def torch_overlap(pos, boxes, k):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--trials", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = H.parser()
     ap.add_argument("--no-million", action="store_true")
     args = ap.parse_args()
     import torch
-    from __graft_entry__ import load_package
 
-    pkg = load_package()
+    pkg = H.load_package()
     N = pkg._native
     lib = N.load_overlap()
     stream = torch.cuda.current_stream()
+    median_ms = H.median_timer(args, slow_ms=500.0)
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        fn()
-        b.record(stream)
-        b.synchronize()
-        return a.elapsed_time(b)
-
-    def median_ms(fn):
-        trials, warmup = args.trials, args.warmup
-        if timed(fn) > 500.0:
-            trials, warmup = 3, 0
-        for _ in range(warmup):
-            fn()
-        times = [timed(fn) for _ in range(trials)]
-        return float(np.median(times)), float(min(times)), float(max(times)), trials
-
-    def entry(boxes, ms, lo, hi, trials):
-        return {"boxes": boxes, "ms": round(ms, 4), "ms_min_max": [round(lo, 4), round(hi, 4)], "trials": trials,
-                "Mboxes_s": round(boxes / ms / 1e3, 4)}
+    def entry(boxes, t):
+        return H.entry(t, "Mboxes_s", boxes, boxes=boxes)
 
     def launcher(scene, d_boxes, k, any_only, d_out, d_cnt):
         op = pkg.tracer.overlap_params(k, any_only)
@@ -116,9 +92,9 @@ def main():
             row[f"per_box_{name}"] = {k: round(c[k] / len(sample), 2) for k in ("node_visits", "leaf_visits", "triangle_tests")}
             if not any_only:
                 row["n_mean"], row["n_max"], row["touched"] = round(float(cnt.mean()), 2), int(cnt.max()), round(float((cnt > 0).mean()), 4)
-        row["counts_only"] = entry(len(d_boxes), *median_ms(launcher(scene, d_boxes, 0, False, d_out, d_cnt)))
-        row["K8_counts"] = entry(len(d_boxes), *median_ms(launcher(scene, d_boxes, 8, False, d_out, d_cnt)))
-        row["any"] = entry(len(d_boxes), *median_ms(launcher(scene, d_boxes, 0, True, d_out, d_cnt)))
+        row["counts_only"] = entry(len(d_boxes), median_ms(launcher(scene, d_boxes, 0, False, d_out, d_cnt)))
+        row["K8_counts"] = entry(len(d_boxes), median_ms(launcher(scene, d_boxes, 8, False, d_out, d_cnt)))
+        row["any"] = entry(len(d_boxes), median_ms(launcher(scene, d_boxes, 0, True, d_out, d_cnt)))
         row["any_over_counts_only"] = round(row["any"]["ms"] / row["counts_only"]["ms"], 4)
         print(f"  {row['counts_only']['ms']} / {row['K8_counts']['ms']} / {row['any']['ms']} ms", file=sys.stderr, flush=True)
         return row
@@ -145,30 +121,26 @@ def main():
         w /= w.sum(1, keepdims=True)
         centre = (tris[t] * w[:, :, None]).sum(1)
         half = F(0.025 * extent)
-        d_near = torch.from_numpy(pkg.tracer.make_boxes(centre - half, centre + half).view(F).reshape(-1, 8).copy()).cuda()
+        d_near = H.upload(pkg.tracer.make_boxes(centre - half, centre + half), 8)
         res["surface_5pct"] = forms(scene, d_near)
         return res, d_near
 
     out = {"trials": args.trials, "warmup": args.warmup, "device": torch.cuda.get_device_name(0)}
-    world = pkg.World(pkg.scenes.bunny_trisrc())
-    pos = np.asarray(world.arrays()["vertex_positions"], F)
-    scene = pkg.Scene(world.flatten())
-    out["bunny"], d_near = scene_cases(scene, pos)
-    out["bunny"]["triangles"] = len(pos) // 9
+    with H.bunny_scene(pkg) as (world, scene, pos):
+        out["bunny"], d_near = scene_cases(scene, pos)
+        out["bunny"]["triangles"] = len(pos) // 9
 
-    # what a caller would write today: every box against every triangle in torch, on 2^12 of the 5 % boxes
-    few = d_near[: 1 << 12].contiguous()
-    d_pos = torch.from_numpy(pos).cuda()
-    want, want_n = torch_overlap(d_pos, few, 8)
-    got, got_n = scene.triangles_in_boxes(few, max_triangles=8)
-    assert bool((got == want).all()) and bool((got_n == want_n).all())
-    d_out = torch.empty((len(few), 8), dtype=torch.int32, device="cuda")
-    d_cnt = torch.empty(len(few), dtype=torch.int32, device="cuda")
-    ours = entry(len(few), *median_ms(launcher(scene, few, 8, False, d_out, d_cnt)))
-    brute = entry(len(few), *median_ms(lambda: torch_overlap(d_pos, few, 8)))
-    out["torch_vs_k8"] = {"kernel": ours, "torch": brute, "torch_over_kernel": round(brute["ms"] / ours["ms"], 2)}
-    scene.close()
-    world.close()
+        # what a caller would write today: every box against every triangle in torch, on 2^12 of the 5 % boxes
+        few = d_near[: 1 << 12].contiguous()
+        d_pos = torch.from_numpy(pos).cuda()
+        want, want_n = torch_overlap(d_pos, few, 8)
+        got, got_n = scene.triangles_in_boxes(few, max_triangles=8)
+        assert bool((got == want).all()) and bool((got_n == want_n).all())
+        d_out = torch.empty((len(few), 8), dtype=torch.int32, device="cuda")
+        d_cnt = torch.empty(len(few), dtype=torch.int32, device="cuda")
+        ours = entry(len(few), median_ms(launcher(scene, few, 8, False, d_out, d_cnt)))
+        brute = entry(len(few), median_ms(lambda: torch_overlap(d_pos, few, 8)))
+        out["torch_vs_k8"] = {"kernel": ours, "torch": brute, "torch_over_kernel": round(brute["ms"] / ours["ms"], 2)}
 
     if not args.no_million:
         dw = pkg.tracer.DeviceWorld(pkg.scenes.million_obj())
@@ -176,7 +148,7 @@ def main():
         out["million"], _ = scene_cases(dw.scene, pos)
         out["million"]["triangles"] = len(pos) // 9
         dw.close()
-    print(json.dumps(out))
+    H.emit(out, args)
 
 
 if __name__ == "__main__":

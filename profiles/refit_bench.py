@@ -12,17 +12,13 @@ the vertical axis with a radial bulge and 1 % seeded noise):
 
 Times: median of --trials after --warmup, bracketed by HIP events on the current torch stream (the host-blocking calls (a)
 and (b) also as host wall time).  Usage: python profiles/refit_bench.py [--trials 15] [--warmup 5]"""
-import argparse
 import ctypes as C
-import json
-import os
-import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
+import bench_harness as H
+from bench_workloads import camera_rays
 
 F = np.float32
 
@@ -43,17 +39,13 @@ def twist(vd, seed=7):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--trials", type=int, default=15)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap = H.parser()
     args = ap.parse_args()
     import torch
     import bench
     import ray_query_ref as RQ
-    from ray_query_bench import camera_rays
-    from __graft_entry__ import load_package
 
-    pkg = load_package()
+    pkg = H.load_package()
     N = pkg._native
     hip = N.load_hip()
     stream = torch.cuda.current_stream()
@@ -75,7 +67,7 @@ def main():
                 "wall_ms": round(float(np.median(wall)), 4)}
 
     out = {"trials": args.trials, "warmup": args.warmup, "device": torch.cuda.get_device_name(0), "scenes": []}
-    W, H = 1920, 1080
+    W, HEIGHT = 1920, 1080
     for label, path in (("bunny-class trisrc", pkg.scenes.bunny_trisrc()), ("1M-triangle obj", pkg.scenes.million_obj())):
         world = pkg.tracer.DeviceWorld(path, pkg.scenes.environment_constant(), device=0)
         lib = N.load_host()
@@ -136,12 +128,12 @@ def main():
         hip.shray_device_tree_destroy(tree)
 
         # (c) primary rays of the headline view on both scenes
-        params = bench.orbit_params(pkg, world, W, H)[0]
-        o, d = camera_rays(params, W, H, RQ.xform)
-        rays = torch.from_numpy(pkg.tracer.make_rays(o, d, F(1e7)).view(np.float32).reshape(-1, 8).copy()).cuda()
-        hits = torch.empty((W * H, 4), dtype=torch.int32, device="cuda")
+        params = bench.orbit_params(pkg, world, W, HEIGHT)[0]
+        o, d = camera_rays(params, W, HEIGHT, RQ.xform)
+        rays = H.upload(pkg.tracer.make_rays(o, d, F(1e7)), 8)
+        hits = torch.empty((W * HEIGHT, 4), dtype=torch.int32, device="cuda")
         for key, sc in (("c_primary_refit", world.scene), ("c_primary_rebuilt", rebuilt_scene)):
-            row[key] = median(lambda: sc.trace_rays_into(rays.data_ptr(), W * H, hits.data_ptr(), stream.cuda_stream))
+            row[key] = median(lambda: sc.trace_rays_into(rays.data_ptr(), W * HEIGHT, hits.data_ptr(), stream.cuda_stream))
             torch.cuda.synchronize()
             row[key]["hit_fraction"] = round(float((hits[:, 3] >= 0).float().mean().item()), 4)
         row["sah_cost_refit"] = round(refit_stats["sah_cost"], 4)
@@ -150,7 +142,7 @@ def main():
         out["scenes"].append(row)
         rebuilt_scene.close()
         world.close()
-    print(json.dumps(out))
+    H.emit(out, args)
 
 
 if __name__ == "__main__":
